@@ -20,8 +20,11 @@ one-shot index build of the batch is outside the timed region and reported separ
 config.strong_scaling_proxy: the step and the fresh-batch index build of ONE eighth of the batch on this GPU and the
 efficiency t(batch) / (8 t(eighth)) an 8-GPU run could reach before the all-reduce.
 
-Rank 0 prints ONE JSON line with `roofline` (gather/segment-sum kernel, HIP events on the launch stream) and
-`cpu_baseline` (oracle port timed on the host cores, bounded sample).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line from rank 0 (`roofline` null).  `--full` adds
+what the headline figure does not need: the `roofline` leg (the conv's gather-scatter launches replayed on their own, HIP
+events on the launch stream), the strong-scaling proxy, the fresh-batch leg, the GIN leg, the other configurations
+(`secondary`) and `cpu_baseline` (oracle port timed on the host cores, bounded sample).  `--steady` keeps the roofline leg
+without --full.  `--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy, see dump_outputs.
 """
 import argparse
 import json
@@ -37,6 +40,34 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_BUDGET = 15000000  # elements over all arrays of --dump-outputs (60 MB of float32: two builds are compared file by file)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32 (float64 tensors stay float64).  Arrays are written smallest
+    first, each up to an equal share of what is left of DUMP_BUDGET; a larger one is cut to a fixed, seeded sample of its
+    rows (the same rows for arrays of the same shape), whose indices go to <name>_rows.npy.  -> {name: shape written}"""
+    os.makedirs(out_dir, exist_ok=True)
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left, written = DUMP_BUDGET, {}
+    for i, (name, t) in enumerate(todo):
+        t = t.detach()
+        share = left // (len(todo) - i)
+        if t.dim() >= 1 and t.numel() > share:
+            k = max(1, share // (t.numel() // t.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=k, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.size
+        written[name] = list(a.shape)
+    return written
+
+
+def grads_of(module):
+    """{grad_<parameter name>: .grad} of the parameters that have one (the flat bucket's views after a step)."""
+    return {"grad_" + n.replace(".", "_"): p.grad for n, p in module.named_parameters() if p.grad is not None}
 
 
 def shard_of(raw, rank, world):
@@ -239,11 +270,13 @@ def run_config4(args, rank, world, dev, emit=True):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        loss = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if rank == 0 and getattr(args, "dump_outputs", ""):
+        dump_outputs(args.dump_outputs, dict(grads_of(model), loss=loss))
     tot = torch.tensor([float(E), float(N)], device=dev, dtype=torch.float64)
     tt = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
@@ -404,8 +437,15 @@ def main():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="config5 / config3: strong = ONE global batch cut by parallel.shard_graphs (default); weak = a full batch per rank")
     ap.add_argument("--no-proxy", action="store_true", help="skip the one-GPU strong-scaling proxy (an eighth of the batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline step: roofline leg, strong-scaling proxy, fresh-batch leg, GIN leg, "
+                         "the other configurations (secondary) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy (float32, at most 60 MB: "
+                         "a fixed, seeded row sample of the larger arrays)")
     ap.add_argument("--steady", action="store_true",
-                    help="profiling aid: the replayed step and the roofline leg only (no fresh-batch leg, GIN leg, proxy, CPU baseline)")
+                    help="profiling aid: the replayed step and the roofline leg only, with or without --full (no fresh-batch leg, GIN "
+                         "leg, proxy, CPU baseline)")
     ap.add_argument("--dtype", default="", choices=["", "bf16", "f32"])
     ap.add_argument("--hidden", type=int, default=0, help="override the workload's hidden size (experiments only)")
     ap.add_argument("--act", default="relu", choices=["relu", "leaky_relu"],
@@ -416,8 +456,11 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the config 3 / config 4 / proteins legs of the default line")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured HIP graph")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.steady:
         args.no_proxy = args.no_cpu_baseline = True
+    roofline_leg = args.full or args.steady
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(spawn_ranks(args))             # nothing in this process has touched the GPU yet
@@ -496,12 +539,16 @@ def main():
         ix, first_ms = build_index()            # first call: allocator growth + code-object load
         ix, steady_ms = build_index()           # steady state (what a training loop pays per new batch)
 
+        res = {}
+
         def compute():
             bucket.zero(set_to_none=True)       # optimizer.zero_grad()'s default (train.py:836): gradients are written, not added
             xb.grad = None
             out, _ = layer(gb, xb, et)
             out.backward(gob)
             bucket.pack()                       # the step's gradients -> the flat bucket (one launch), inside the captured step
+            if args.dump_outputs:               # the captured call's output is the buffer every replay writes; detached, so
+                res["out"] = out.detach()       # that the step's autograd graph is not kept alive into the next capture
 
         def step_eager():
             compute()
@@ -537,7 +584,7 @@ def main():
             else:
                 step_eager()
 
-        return dict(step=step, graph=gr, index=ix, index_ms=(first_ms, steady_ms), x=xb, gout=gob)
+        return dict(step=step, graph=gr, index=ix, index_ms=(first_ms, steady_ms), x=xb, gout=gob, res=res)
 
     main = prepare(g, 100 + rank)
     step, graph, index, x, gout = main["step"], main["graph"], main["index"], main["x"], main["gout"]
@@ -563,6 +610,9 @@ def main():
         te = torch.tensor([float(E)], device=dev, dtype=torch.float64)
         dist.all_reduce(te)
         e_glob = float(te.item())               # strong: the global batch's edges; weak: world x E
+    ms_per_step = dt / args.steps * 1e3
+    if rank == 0 and args.dump_outputs:         # before anything below runs the layer again
+        dump_outputs(args.dump_outputs, dict(grads_of(layer), out=main["res"]["out"], x_grad=x.grad))
 
     # roofline leg: the conv's gather-scatter launches alone (gather/segment-sum + gathered-row transform of the forward
     # and of the input-gradient pass, exactly the launches the step makes), replayed as their own HIP graph and timed with
@@ -591,14 +641,6 @@ def main():
                 gy = ops.gather_segsum(gout, index.seg_dst, None)
                 ops.gather_segsum(gy, index.seg_by_src, index.optr, N)
 
-    cg_out = torch.empty((N, H), dtype=dtype, device=dev)
-    conv_gather_scatter()
-    torch.cuda.synchronize()
-    timer = ops.KernelTimer()
-    ops.kernel_timer = timer
-    conv_gather_scatter()                               # eager pass: counts the launches (times include launch gaps)
-    ops.kernel_timer = None
-    n_launch = len(timer.records)
     def graphed(fn):
         """fn replayed from a HIP graph; falls back to the eager callable if the capture fails."""
         try:
@@ -613,22 +655,30 @@ def main():
             torch.cuda.synchronize()
             return fn
 
-    replay_conv = graphed(conv_gather_scatter)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = max(args.steps, 5)
-    e0.record()
-    for _ in range(reps):
-        replay_conv()
-    e1.record()
-    torch.cuda.synchronize()
-    kernel_ms_step = e0.elapsed_time(e1) / reps
-    ms_per_step = dt / args.steps * 1e3
+    if roofline_leg:
+        cg_out = torch.empty((N, H), dtype=dtype, device=dev)
+        conv_gather_scatter()
+        torch.cuda.synchronize()
+        timer = ops.KernelTimer()
+        ops.kernel_timer = timer
+        conv_gather_scatter()                           # eager pass: counts the launches (times include launch gaps)
+        ops.kernel_timer = None
+        n_launch = len(timer.records)
+        replay_conv = graphed(conv_gather_scatter)
+        reps = max(args.steps, 5)
+        e0.record()
+        for _ in range(reps):
+            replay_conv()
+        e1.record()
+        torch.cuda.synchronize()
+        kernel_ms_step = e0.elapsed_time(e1) / reps
 
     # strong-scaling proxy (rank 0, one GPU): ONE eighth of the global batch (the shard rank 0 of an 8-GPU run takes) on this
     # GPU -- step under HIP-graph replay incl. bucket.pack(), fresh-batch index build -- and the efficiency an 8-GPU run could
     # reach before the gradient all-reduce: t(batch) / (8 t(eighth)).  No multi-GPU curve is measured here.
     proxy = None
-    if rank == 0 and world == 1 and strong and not args.no_proxy and graphs >= 8:
+    if args.full and rank == 0 and world == 1 and strong and not args.no_proxy and graphs >= 8:
         g8, raw8, aug8 = build_batch(dev, seed0, graphs, args.workload, shard=(0, 8))
         p8 = prepare(g8, 100)
         # (8 x the warm-up and the steps of the main leg: the same GPU time -- 20 steps of 0.55 ms behind a second of batch and
@@ -681,7 +731,7 @@ def main():
     # build run on a side stream while the current step replays (what the reference's DataLoader workers do for dgl.batch on
     # the CPU): per-step wall time of the overlapped loop.
     overlapped_ms = None
-    if rank == 0 and world == 1 and graph is not None and fused and dtype == torch.bfloat16 and not args.steady:
+    if args.full and rank == 0 and world == 1 and graph is not None and fused and dtype == torch.bfloat16 and not args.steady:
         from dummynode4graphlearning_amd import transforms as _tr
         side2 = torch.cuda.Stream()                     # (a high-priority side stream changes nothing: 0.88 vs 0.89 G edges/s)
         traw = {k: torch.from_numpy(v).to(dev) for k, v in raw.items() if isinstance(v, np.ndarray)}
@@ -711,29 +761,33 @@ def main():
 
     # roofline: algorithmic bytes of the layer's gather-scatter forward+backward (SURVEY.md 8d:
     # 2*(E*H*s + N*H*s + 8*E)) over the time of the launches that implement it
-    launches_per_step = n_launch
-    alg_bytes_step = 2.0 * (E * H * s + N * H * s + 8.0 * E)
-    achieved = alg_bytes_step / (kernel_ms_step * 1e-3) / 1e9 if kernel_ms_step > 0 else 0.0
+    roofline = None
+    if roofline_leg:
+        alg_bytes_step = 2.0 * (E * H * s + N * H * s + 8.0 * E)
+        achieved = alg_bytes_step / (kernel_ms_step * 1e-3) / 1e9 if kernel_ms_step > 0 else 0.0
 
-    # HBM traffic of those launches comes from PMC counters, which cannot be read from inside the process: it is taken
-    # from the committed rocprofv3 measurement of this exact workload (profiles/rNN_traffic.json), else null
-    traffic = None
-    from dummynode4graphlearning_amd._lib import source_digest
-    for tag in ("r06", "r05", "r04", "r03", "r02", "r01"):                    # newest committed measurement of this exact workload AND code
-        try:
-            with open(os.path.join(ROOT, "profiles", tag + "_traffic.json")) as f:
-                tj = json.load(f)
-            if ((tj["workload"], tj["N"], tj["E"], tj["H"], tj["dtype"]) == (args.workload, N, E, H, "bf16" if dtype == torch.bfloat16 else "f32")
-                    and tj.get("source_sha16") == source_digest()):
-                traffic = tj["conv_gather_scatter_hbm_bytes_per_step"]
-                break
-        except Exception:
-            continue
+        # HBM traffic of those launches comes from PMC counters, which cannot be read from inside the process: it is taken
+        # from the committed rocprofv3 measurement of this exact workload (profiles/rNN_traffic.json), else null
+        traffic = None
+        from dummynode4graphlearning_amd._lib import source_digest
+        for tag in ("r06", "r05", "r04", "r03", "r02", "r01"):                # newest committed measurement of this exact workload AND code
+            try:
+                with open(os.path.join(ROOT, "profiles", tag + "_traffic.json")) as f:
+                    tj = json.load(f)
+                if ((tj["workload"], tj["N"], tj["E"], tj["H"], tj["dtype"]) == (args.workload, N, E, H, "bf16" if dtype == torch.bfloat16 else "f32")
+                        and tj.get("source_sha16") == source_digest()):
+                    traffic = tj["conv_gather_scatter_hbm_bytes_per_step"]
+                    break
+            except Exception:
+                continue
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic, "kernel": "rows_transform_ring_kernel + rows_close_ring_kernel (the conv's launches, both directions)",
+                    "launches_per_step": n_launch, "kernel_ms_per_step": kernel_ms_step, "alg_bytes_per_step": alg_bytes_step}
 
     # secondary line (rank 0, N = 1): the pure gather -> segment-sum kernel on a GIN conv (no relation transform), forward
     # + backward, on a PROTEINS-shaped dummy-augmented batch (SURVEY 8d config 2 x 32 graphs, fp32 H = 128)
     gin = None
-    if rank == 0 and world == 1 and not args.steady:
+    if args.full and rank == 0 and world == 1 and not args.steady:
         from dummynode4graphlearning_amd import synthetic as syn, transforms as tr
         r2 = syn.config2(graphs=16384)
         t2 = {k: torch.from_numpy(v).to(dev) for k, v in r2.items()}
@@ -773,7 +827,8 @@ def main():
     # own precision and in bf16, one rank of config 4, and the config-5 layer on PROTEINS-shaped graphs.  They run LAST: nothing
     # above is timed behind them.
     secondary = {}
-    if rank == 0 and world == 1 and args.workload == "config5" and not args.steady and not args.no_secondary and not args.graphs:
+    if (args.full and rank == 0 and world == 1 and args.workload == "config5" and not args.steady and not args.no_secondary
+            and not args.graphs):
         from types import SimpleNamespace
         for key, (wl, dt_) in (("config3_f32", ("config3", torch.float32)), ("config3_bf16", ("config3", torch.bfloat16)),
                                ("proteins_bf16", ("proteins", torch.bfloat16))):
@@ -812,17 +867,13 @@ def main():
                        "edges_per_s_fresh_batch_overlapped": (E / (overlapped_ms * 1e-3)) if overlapped_ms else None,
                        "grad_bucket_bytes": bucket.bytes(), "hip_graph": graph is not None,
                        "sub_batches": len(index.parts) if hasattr(index, "parts") else 1},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": "rows_transform_ring_kernel + rows_close_ring_kernel (the conv's launches, both directions)",
-                         "launches_per_step": launches_per_step, "kernel_ms_per_step": kernel_ms_step,
-                         "alg_bytes_per_step": alg_bytes_step},
+            "roofline": roofline,
         }
         if gin is not None:
             line["secondary"] = {"gin_conv_gather": gin}
         if secondary:
             line.setdefault("secondary", {}).update(secondary)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(raw, H, R)
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

@@ -171,6 +171,26 @@ def test_cpu_baseline_port_equals_reference_formulation(golden_dir):
     assert done >= 3
 
 
+def test_bench_dump_outputs_keeps_its_budget_and_a_fixed_row_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: small arrays whole (bf16 as float32, float64 kept), larger ones cut to a seeded row sample that
+    is the same from run to run and for arrays of the same shape, all of it within DUMP_BUDGET elements."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1000)
+    big = torch.arange(400 * 4, dtype=torch.float32).reshape(400, 4)
+    arrays = {"out": big, "x_grad": -big, "grad_w": torch.ones(3, 5, dtype=torch.bfloat16), "loss": torch.tensor(2.5, dtype=torch.float64)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    ld = lambda d, n: np.load(str(tmp_path / d / (n + ".npy")))  # noqa: E731
+    assert shapes["grad_w"] == [3, 5] and ld("a", "grad_w").dtype == np.float32 and (ld("a", "grad_w") == 1).all()
+    assert ld("a", "loss").dtype == np.float64 and float(ld("a", "loss")) == 2.5
+    rows = ld("a", "out_rows").astype(np.int64)
+    assert 0 < len(rows) < 400 and (np.diff(rows) > 0).all() and (ld("a", "x_grad_rows") == rows).all()
+    assert shapes["out"] == shapes["x_grad"] == [len(rows), 4]
+    assert (ld("a", "out") == big.numpy()[rows]).all() and (ld("a", "x_grad") == -big.numpy()[rows]).all()
+    assert (ld("b", "out") == ld("a", "out")).all()
+    assert sum(int(np.prod(s)) for s in shapes.values()) <= 1000
+
+
 def test_synthetic_configs_have_the_survey_shapes():
     from dummynode4graphlearning_amd import synthetic
     from oracle import transforms as OT

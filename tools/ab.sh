@@ -8,7 +8,7 @@ VALS=()
 while [ "$1" != "--" ] && [ -n "$1" ]; do VALS+=("$1"); shift; done
 shift
 for v in "${VALS[@]}"; do
-  env "$VAR=$v" python bench.py --no-cpu-baseline --steps 30 --warmup 5 "$@" 2>/dev/null | python -c "
+  env "$VAR=$v" python bench.py --full --no-cpu-baseline --steps 30 --warmup 5 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 r = d['roofline']

@@ -4,6 +4,7 @@ VAR=$1; shift
 VALS=()
 while [ "$1" != "--" ] && [ -n "$1" ]; do VALS+=("$1"); shift; done
 shift
+set -- --full "$@"          # the summary below reads the roofline, proxy and fresh-batch fields
 k=0
 for v in "${VALS[@]}"; do
   k=$((k + 1))

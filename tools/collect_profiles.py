@@ -4,7 +4,7 @@
     python tools/collect_profiles.py --tag r01 [--out gpurun_out/profiles]
 
 Runs (each as a child process, the profiled program directly after `--`):
-  1. python bench.py                                             -> <tag>_bench_line.json
+  1. python bench.py --full                                      -> <tag>_bench_line.json
   2. rocprofv3 --kernel-trace --stats        -- python3 bench.py --steps 20 --warmup 5 --steady
                                                                  -> <tag>_kernel_stats.csv   (the replayed step and the roofline
                                                                     leg only: AverageNs of the conv kernels reproduces the line)
@@ -283,7 +283,7 @@ def main():
     import shutil
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     shutil.copy(os.path.join(a.out, a.tag + "_traffic.json"), os.path.join(ROOT, "profiles", a.tag + "_traffic.json"))
-    r = run(["python3", bench])
+    r = run(["python3", bench, "--full"])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:
         sys.stderr.write(r.stderr[-2000:])

@@ -1,11 +1,12 @@
-# GPU box: the kernel / layer tests + the default bench line summary + per-kernel averages of a --steady run; fails on a GPU fault
+# GPU box: the kernel / layer tests + the --full bench line summary + per-kernel averages of a --steady run; fails on a GPU fault
 cd $GRAFT_REPO_ROOT
 o=gpurun_out/quick_check.txt
+d=$(dirname $o)
 timeout -k 10 900 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_layers.py tests/test_gpu_fuzz.py -x -q > $o 2>&1; rc=$?
 tail -3 $o
 grep -q "Memory access fault" $o && exit 1
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py --no-cpu-baseline > gpurun_out/bench_line.json 2> gpurun_out/bench_line.err; rc=$?
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $d/bench_line.json 2> $d/bench_line.err; rc=$?
 grep -q "Memory access fault" gpurun_out/bench_line.err && exit 1
 python - <<'PY'
 import json

@@ -1,11 +1,12 @@
-# GPU box: the whole -m gpu suite + the default bench line; fails when the runtime reports a fault
+# GPU box: the whole -m gpu suite + the bench line of --full; fails when the runtime reports a fault
 cd $GRAFT_REPO_ROOT
 o=gpurun_out/gpu_tests.txt
+d=$(dirname $o)
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $o 2>&1; rc=$?
 tail -5 $o
 grep -q "Memory access fault" $o && exit 1
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py > gpurun_out/bench_line.json 2> gpurun_out/bench_line.err; rc=$?
+timeout -k 10 300 python bench.py --full > $d/bench_line.json 2> $d/bench_line.err; rc=$?
 grep -q "Memory access fault" gpurun_out/bench_line.err && exit 1
 python - <<'PY'
 import json
