@@ -122,6 +122,22 @@ _SIGS = {
     "dn_batchnorm_rows_bwd_bf16": (ctypes.c_int, [P, P, c_i64, c_i32, P, P, P, P, c_i32, P, P, P, P, c_sz, P]),
     "dn_edge_norm_f32": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i64] + [P] * 7 + [P]),
     "dn_degrees_i32": (ctypes.c_int, [c_i64, c_i64, P, P, P, P, P]),
+    "dn_si_filter_meta_f32": (ctypes.c_int, [c_i64, P, P, P, c_i64, P, P, P, c_i64, c_i32, c_i32, c_i32, c_i32, P, P, P]),
+    "dn_si_filter_meta_bf16": (ctypes.c_int, [c_i64, P, P, P, c_i64, P, P, P, c_i64, c_i32, c_i32, c_i32, c_i32, P, P, P]),
+    "dn_si_embed_fwd_f32": (ctypes.c_int, [c_i64, c_i32, P, P, c_i32, c_i32, P, P, P, c_i32, c_i32, P, P, P]),
+    "dn_si_embed_fwd_bf16": (ctypes.c_int, [c_i64, c_i32, P, P, c_i32, c_i32, P, P, P, c_i32, c_i32, P, P, P]),
+    "dn_si_embed_wgrad_workspace_bytes": (c_sz, [c_i64, c_i32, c_i32]),
+    "dn_si_embed_wgrad_f32": (ctypes.c_int, [c_i64, c_i32, P, P, c_i32, c_i32, P, P, P, c_sz, P]),
+    "dn_si_embed_wgrad_bf16": (ctypes.c_int, [c_i64, c_i32, P, P, c_i32, c_i32, P, P, P, c_sz, P]),
+    "dn_si_pool_sum_f32": (ctypes.c_int, [c_i64, P, P, P, P, c_i32, c_i32, P, P, c_i32, c_i32, P, P, P, c_i32, P, P, P]),
+    "dn_si_pool_sum_bf16": (ctypes.c_int, [c_i64, P, P, P, P, c_i32, c_i32, P, P, c_i32, c_i32, P, P, P, c_i32, P, P, P]),
+    "dn_si_pool_sum_bwd_f32": (ctypes.c_int, [c_i64, P, P, P, c_i32, c_i32, c_i32, P, P]),
+    "dn_si_pool_sum_bwd_bf16": (ctypes.c_int, [c_i64, P, P, P, c_i32, c_i32, c_i32, P, P]),
+    "dn_si_pool_max_f32": (ctypes.c_int, [c_i64, P, P, P, c_i32, P, c_i32, P, P, P]),
+    "dn_si_pool_max_bf16": (ctypes.c_int, [c_i64, P, P, P, c_i32, P, c_i32, P, P, P]),
+    "dn_si_pool_max_bwd_f32": (ctypes.c_int, [c_i64, c_i32, P, P, P, P]),
+    "dn_si_pool_max_bwd_bf16": (ctypes.c_int, [c_i64, c_i32, P, P, P, P]),
+    "dn_si_len_mask_u8": (ctypes.c_int, [c_i64, c_i32, P, P, P, P]),
 }
 
 _lib = None

@@ -2791,3 +2791,223 @@ def linear_any(x, weight, bias=None, exact=None):
             return _LinearActFn.apply(x, weight, bias, False, exact)
         return _LinearAnyFn.apply(x, weight, bias)
     return torch.nn.functional.linear(x, weight, bias)
+
+
+# ----------------------------------------------------------------------------------------------
+# SI count models: the glue of GraphAdjModel.forward around the rep nets (dn_simodel.hip)
+# ----------------------------------------------------------------------------------------------
+SI_FLAGS = ((1, "a node label outside the label table"), (2, "a node id outside the id table"),
+            (4, "a pattern with no nodes"), (8, "a graph with no nodes"), (16, "inconsistent node_ptr"))
+
+
+def launch_tagged(tag, fn):
+    """fn() under kernel_timer's tag when a timer is set (the tags show which SI model path ran)."""
+    if kernel_timer is not None:
+        return kernel_timer.launch(tag, fn)
+    return fn()
+
+
+def _u8_or_none(t):
+    """The is_dummy node flag as uint8 [N] (bool is viewed, not copied)."""
+    if t is None:
+        return None
+    t = t.reshape(-1)
+    if t.dtype == torch.bool:
+        return t.view(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise _lib.DnHipError("dummy flags must be bool or uint8 on the device (got %s)" % t.dtype)
+    return t
+
+
+def si_filter_meta(p_ptr, p_label, p_id, g_ptr, g_label, g_id, p_sizes, g_sizes, gate_dtype=None):
+    """(meta int32 [4] on the device = {Lp, Lg, flags, 0}, gate [Ng, 1] in gate_dtype or None) -- dn_si_filter_meta_*.  The
+    table sizes are (labels, ids) per side; ids / labels outside them, zero-node graphs and broken ptrs set flag bits."""
+    require_gpu(p_ptr, p_label, p_id, g_ptr, g_label, g_id)
+    for t, n in ((p_ptr, "p_ptr"), (p_label, "p_label"), (p_id, "p_id"), (g_ptr, "g_ptr"), (g_label, "g_label"), (g_id, "g_id")):
+        _i32(t, n)
+    B = p_ptr.numel() - 1
+    if B < 1 or g_ptr.numel() != B + 1:
+        raise _lib.DnHipError("si_filter_meta: pattern and graph batches need the same B >= 1 graphs")
+    meta = torch.empty(4, dtype=I32, device=p_ptr.device)
+    gate = None
+    dt = gate_dtype if gate_dtype is not None else torch.float32
+    if gate_dtype is not None:
+        gate = torch.empty((g_label.numel(), 1), dtype=gate_dtype, device=g_label.device)
+    fn = getattr(lib(), "dn_si_filter_meta_" + ("bf16" if dt == torch.bfloat16 else "f32"))
+
+    def _launch():
+        check(fn(B, ptr(p_ptr), ptr(p_label), ptr(p_id), p_label.numel(), ptr(g_ptr), ptr(g_label), ptr(g_id), g_label.numel(),
+                 int(p_sizes[0]), int(p_sizes[1]), int(g_sizes[0]), int(g_sizes[1]), ptr(gate), ptr(meta), stream_ptr()),
+              "dn_si_filter_meta")
+    launch_tagged("si_filter" if gate is not None else "si_meta", _launch)
+    return meta, gate
+
+
+def si_read_meta(meta):
+    """THE device-to-host read of an SI model forward: (Lp, Lg); raises on the flags the kernels set (ValueError for zero-node
+    graphs, whose padded mask the reference gets wrong; DnHipError for ids / labels / ptrs out of range)."""
+    lp, lg, flags, _ = meta.tolist()
+    if flags:
+        what = "; ".join(m for bit, m in SI_FLAGS if flags & bit)
+        if flags & (4 | 8):
+            raise ValueError("SI model batch: %s" % what)
+        raise _lib.DnHipError("SI model batch: %s" % what)
+    return int(lp), int(lg)
+
+
+def _embed_tables(parts):
+    """parts: [(key int32 [N], enc [rows, K], W [K, H])] -> flat launch arguments of one or two tables."""
+    args = []
+    for i in range(2):
+        if i < len(parts):
+            key, enc, W = parts[i]
+            args += [ptr(key), ptr(enc), int(enc.shape[0]), int(enc.shape[1]), ptr(W)]
+        else:
+            args += [None, None, 0, 0, None]
+    return args
+
+
+class _SiEmbedFn(torch.autograd.Function):
+    """emb[v] = enc_vl[label_v] @ W_vl (+ enc_v[id_v] @ W_v): dn_si_embed_fwd_* / dn_si_embed_wgrad_*.  The enc tables are frozen
+    (basemodel.py:669-670): no gradient to them or to the keys."""
+
+    @staticmethod
+    def forward(ctx, key1, enc1, W1, key2, enc2, W2):
+        parts = [(key1, enc1.contiguous(), W1.contiguous())]
+        if key2 is not None:
+            parts.append((key2, enc2.contiguous(), W2.contiguous()))
+        require_gpu(*[t for p in parts for t in p])
+        for key, enc, W in parts:
+            _i32(key, "key")
+            if enc.dtype != W.dtype or W.shape[0] != enc.shape[1] or key.numel() != key1.numel():
+                raise _lib.DnHipError("si_embed: enc [rows, K], W [K, H] of one dtype and one key per row expected")
+        N, H = key1.numel(), int(W1.shape[1])
+        if key2 is not None and W2.shape[1] != H:
+            raise _lib.DnHipError("si_embed: both tables must embed into the same width")
+        out = torch.empty((N, H), dtype=W1.dtype, device=W1.device)
+        fn = getattr(lib(), "dn_si_embed_fwd_" + _suffix(W1))
+        launch_tagged("si_embed", lambda: check(fn(N, H, *_embed_tables(parts), ptr(out), stream_ptr()), "dn_si_embed_fwd"))
+        ctx.parts = len(parts)
+        ctx.save_for_backward(*[t for p in parts for t in p])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        g = g.contiguous()
+        grads = [None] * 6
+        for i in range(ctx.parts):
+            key, enc, W = saved[3 * i:3 * i + 3]
+            if not ctx.needs_input_grad[3 * i + 2]:
+                continue
+            grads[3 * i + 2] = si_embed_wgrad(key, enc, g)
+        return tuple(grads)
+
+
+def si_embed(key1, enc1, W1, key2=None, enc2=None, W2=None):
+    return _SiEmbedFn.apply(key1, enc1, W1, key2, enc2, W2)
+
+
+def si_embed_wgrad(key, enc, g):
+    """dW [K, H] = enc[key]^T @ g, deterministic (dn_si_embed_wgrad_*)."""
+    require_gpu(key, enc, g)
+    N, H, K = g.shape[0], g.shape[1], enc.shape[1]
+    dW = torch.empty((K, H), dtype=g.dtype, device=g.device)
+    ws = _ws(lib().dn_si_embed_wgrad_workspace_bytes(N, K, H), g.device)
+    fn = getattr(lib(), "dn_si_embed_wgrad_" + _suffix(g))
+    launch_tagged("si_embed_wgrad", lambda: check(fn(N, H, ptr(_i32(key, "key")), ptr(enc.contiguous()), int(enc.shape[0]), K, ptr(g), ptr(dW),
+                                              ptr(ws), ws.numel(), stream_ptr()), "dn_si_embed_wgrad"))
+    return dW
+
+
+class _SiPoolSumFn(torch.autograd.Function):
+    """pooled [B, D] fp32 = per-graph sum of the non-dummy virtual rows [enc_v(id) | enc_vl(label) | out_deg | in_deg | rep]
+    (dn_si_pool_sum_*); the gradient reaches rep only (encoders frozen, degrees integer)."""
+
+    @staticmethod
+    def forward(ctx, rep, node_ptr, dummy, id_, enc_v, label, enc_vl, out_deg, in_deg):
+        rep = rep.contiguous()
+        require_gpu(rep, node_ptr, dummy, id_, enc_v, label, enc_vl, out_deg, in_deg)
+        B, H = node_ptr.numel() - 1, rep.shape[1]
+        Kv = int(enc_v.shape[1]) if id_ is not None else 0
+        Kvl = int(enc_vl.shape[1]) if label is not None else 0
+        D = Kv + Kvl + (2 if out_deg is not None else 0) + H
+        for t in (enc_v if id_ is not None else None, enc_vl if label is not None else None):
+            if t is not None and t.dtype != rep.dtype:
+                raise _lib.DnHipError("si_pool_sum: encoder tables must have the dtype of rep")
+        pooled = torch.empty((B, D), dtype=torch.float32, device=rep.device)
+        count = torch.empty(B, dtype=I32, device=rep.device)
+        fn = getattr(lib(), "dn_si_pool_sum_" + _suffix(rep))
+        launch_tagged("si_pool_sum", lambda: check(fn(B, ptr(_i32(node_ptr, "node_ptr")), ptr(dummy), ptr(id_), ptr(enc_v), int(enc_v.shape[0]) if id_ is not None else 0,
+                                               Kv, ptr(label), ptr(enc_vl), int(enc_vl.shape[0]) if label is not None else 0, Kvl,
+                                               ptr(out_deg), ptr(in_deg), ptr(rep), H, ptr(pooled), ptr(count), stream_ptr()),
+                                            "dn_si_pool_sum"))
+        ctx.save_for_backward(node_ptr, dummy if dummy is not None else node_ptr.new_empty(0))
+        ctx.has_dummy, ctx.shape, ctx.dtype, ctx.col0 = dummy is not None, rep.shape, rep.dtype, D - H
+        ctx.mark_non_differentiable(count)
+        return pooled, count
+
+    @staticmethod
+    def backward(ctx, dpooled, _dc):
+        node_ptr, dummy = ctx.saved_tensors
+        if dpooled is None:
+            return (None,) * 9
+        dpooled = dpooled.contiguous().float()
+        B = node_ptr.numel() - 1
+        drep = torch.empty(ctx.shape, dtype=ctx.dtype, device=dpooled.device)
+        fn = getattr(lib(), "dn_si_pool_sum_bwd_" + _suffix(drep))
+        launch_tagged("si_pool_sum_bwd", lambda: check(fn(B, ptr(node_ptr), ptr(dummy) if ctx.has_dummy else None, ptr(dpooled),
+                                                   int(dpooled.shape[1]), ctx.col0, int(ctx.shape[1]), ptr(drep), stream_ptr()),
+                                                "dn_si_pool_sum_bwd"))
+        return (drep,) + (None,) * 8
+
+
+def si_pool_sum(rep, node_ptr, dummy=None, id_=None, enc_v=None, label=None, enc_vl=None, out_deg=None, in_deg=None):
+    return _SiPoolSumFn.apply(rep, node_ptr, _u8_or_none(dummy), id_, enc_v, label, enc_vl, out_deg, in_deg)
+
+
+class _SiPoolMaxFn(torch.autograd.Function):
+    """out [B, C] = per-graph max of Y [N, C] over the non-dummy rows, bias as a candidate when the graph has fewer than L of them
+    (dn_si_pool_max_*); the gradient goes to the argmax row, or to the bias where it won."""
+
+    @staticmethod
+    def forward(ctx, Y, bias, node_ptr, dummy, L):
+        Y, bias = Y.contiguous(), bias.contiguous()
+        require_gpu(Y, bias, node_ptr, dummy)
+        if bias.dtype != Y.dtype or bias.numel() != Y.shape[1]:
+            raise _lib.DnHipError("si_pool_max: bias [C] of the dtype of Y expected")
+        B, C = node_ptr.numel() - 1, Y.shape[1]
+        out = torch.empty((B, C), dtype=Y.dtype, device=Y.device)
+        arg = torch.empty((B, C), dtype=I32, device=Y.device)
+        fn = getattr(lib(), "dn_si_pool_max_" + _suffix(Y))
+        launch_tagged("si_pool_max", lambda: check(fn(B, ptr(_i32(node_ptr, "node_ptr")), ptr(dummy), ptr(Y), C, ptr(bias), int(L), ptr(out),
+                                               ptr(arg), stream_ptr()), "dn_si_pool_max"))
+        ctx.save_for_backward(arg)
+        ctx.shape = Y.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (arg,) = ctx.saved_tensors
+        dout = dout.contiguous()
+        B, C = arg.shape
+        dY = torch.zeros(ctx.shape, dtype=dout.dtype, device=dout.device)
+        fn = getattr(lib(), "dn_si_pool_max_bwd_" + _suffix(dout))
+        launch_tagged("si_pool_max_bwd", lambda: check(fn(B, C, ptr(arg), ptr(dout), ptr(dY), stream_ptr()), "dn_si_pool_max_bwd"))
+        dbias = (dout.float() * (arg < 0)).sum(0).to(dout.dtype)
+        return dY, dbias, None, None, None
+
+
+def si_pool_max(Y, bias, node_ptr, L, dummy=None):
+    return _SiPoolMaxFn.apply(Y, bias, node_ptr, _u8_or_none(dummy), L)
+
+
+def si_len_mask(node_ptr, L, dummy=None):
+    """[B, L] bool: batch_convert_len_to_mask(pre_pad=True) with the dummy positions cleared (dn_si_len_mask_u8)."""
+    dummy = _u8_or_none(dummy)
+    require_gpu(node_ptr, dummy)
+    B = node_ptr.numel() - 1
+    mask = torch.empty((B, int(L)), dtype=torch.bool, device=node_ptr.device)
+    launch_tagged("si_len_mask", lambda: check(lib().dn_si_len_mask_u8(B, int(L), ptr(_i32(node_ptr, "node_ptr")), ptr(dummy),
+                                                                ptr(mask.view(torch.uint8)), stream_ptr()), "dn_si_len_mask"))
+    return mask

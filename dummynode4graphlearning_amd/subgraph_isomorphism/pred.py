@@ -1,6 +1,6 @@
 """Count-prediction heads after the representation net.
 
-Mirror of subgraph_isomorphism/models/pred.py:17-216 (PredictNet, MeanPredictNet, SumPredictNet: same constructor,
+Mirror of subgraph_isomorphism/models/pred.py:17-236 (PredictNet, MeanPredictNet, SumPredictNet, MaxPredictNet: same constructor,
 parameter names `p_fc g_fc pred_fc1 pred_fc2 weight_fc1 weight_fc2`, same `forward(p_rep, p_mask, g_rep, g_mask) ->
 (y, w)`) and of the dummy-node masking that precedes it (models/basemodel.py:905-912).  These are dense products on the
 padded [batch, max_len, dim] tensors that `split_and_batchify_graph_feats` produced -- no message passing; they run on
@@ -83,3 +83,8 @@ class MeanPredictNet(PredictNet):
 class SumPredictNet(PredictNet):
     def agg_graph(self, g_rep, g_mask=None):
         return th.sum(g_rep, dim=1)
+
+
+class MaxPredictNet(PredictNet):
+    def agg_graph(self, g_rep, g_mask=None):
+        return th.max(g_rep, dim=1)[0]

@@ -762,6 +762,72 @@ int dn_edge_norm_f32(int32_t mode, int32_t self_loop, int64_t N, int64_t E, cons
 int dn_degrees_i32(int64_t N, int64_t E, const int32_t* src, const int32_t* dst, int32_t* in_deg,
                    int32_t* out_deg, dn_stream_t stream);
 
+/* ---- SI count models (RGIN / RGCN): the glue of GraphAdjModel.forward around the rep nets (dn_simodel.hip) ----
+ * Batches are ragged: node_ptr [B + 1] per side, rows of graph b = [node_ptr[b], node_ptr[b + 1]).  fp32 accumulation,
+ * fixed-order sums, no float atomics.  dummy (uint8 [N], may be NULL): the is_dummy node flag. */
+#define DN_SI_BAD_LABEL 1
+#define DN_SI_BAD_ID 2
+#define DN_SI_ZERO_PATTERN 4
+#define DN_SI_ZERO_GRAPH 8
+#define DN_SI_BAD_PTR 16
+/* Label filter + batch metadata.  Replaces ScalarFilter + get_filter_gate (subgraph_isomorphism/models/filter.py:10-16,
+ * basemodel.py:830-847) and the length / range facts the forward needs.  meta (int32 [4], zeroed here) = {Lp, Lg, flags, 0}:
+ * the longest pattern / graph and the DN_SI_* bits (labels / ids outside [0, table rows), zero-node graphs, inconsistent ptrs).
+ * gate (may be NULL; [Ng]) = 1 where the label of graph node v occurs in pattern b, or is 0 while pattern b is shorter than Lp
+ * (the reference front-pads patterns with label 0 before it compares), else 0. */
+int dn_si_filter_meta_f32(int64_t B, const int32_t* p_ptr, const int32_t* p_label, const int32_t* p_id, int64_t Np,
+                          const int32_t* g_ptr, const int32_t* g_label, const int32_t* g_id, int64_t Ng, int32_t p_nlab,
+                          int32_t p_nid, int32_t g_nlab, int32_t g_nid, float* gate, int32_t* meta, dn_stream_t stream);
+int dn_si_filter_meta_bf16(int64_t B, const int32_t* p_ptr, const int32_t* p_label, const int32_t* p_id, int64_t Np,
+                           const int32_t* g_ptr, const int32_t* g_label, const int32_t* g_id, int64_t Ng, int32_t p_nlab,
+                           int32_t p_nid, int32_t g_nlab, int32_t g_nid, void* gate, int32_t* meta, dn_stream_t stream);
+/* Code embedding.  Replaces get_*_enc + get_*_emb (basemodel.py:849-873): out[v] = enc1[key1[v]] @ W1 (+ enc2[key2[v]] @ W2
+ * when key2 != NULL), enc [rows, K] the frozen encoder tables, W [K, H] (staged in LDS: (K1 + K2) * H <= 16384; H <= 256,
+ * K <= 64). */
+int dn_si_embed_fwd_f32(int64_t N, int32_t H, const int32_t* key1, const float* enc1, int32_t rows1, int32_t K1,
+                        const float* W1, const int32_t* key2, const float* enc2, int32_t rows2, int32_t K2, const float* W2,
+                        float* out, dn_stream_t stream);
+int dn_si_embed_fwd_bf16(int64_t N, int32_t H, const int32_t* key1, const void* enc1, int32_t rows1, int32_t K1,
+                         const void* W1, const int32_t* key2, const void* enc2, int32_t rows2, int32_t K2, const void* W2,
+                         void* out, dn_stream_t stream);
+/* Its weight gradient dW [K, H] = enc[key]^T @ G over the N rows (H <= 256, K <= 64): fixed 32-row partial sums, then an
+ * ordered reduction. */
+size_t dn_si_embed_wgrad_workspace_bytes(int64_t N, int32_t K, int32_t H);
+int dn_si_embed_wgrad_f32(int64_t N, int32_t H, const int32_t* key, const float* enc, int32_t rows, int32_t K,
+                          const float* G, float* dW, void* workspace, size_t workspace_bytes, dn_stream_t stream);
+int dn_si_embed_wgrad_bf16(int64_t N, int32_t H, const int32_t* key, const void* enc, int32_t rows, int32_t K,
+                           const void* G, void* dW, void* workspace, size_t workspace_bytes, dn_stream_t stream);
+/* Ragged Sum / Mean head pooling.  Replaces the concatenation, padding and masking in front of the pred net
+ * (basemodel.py:914-954, pred.py:17-216): pooled [B, D] fp32 = sum over the non-dummy rows of graph b of
+ * [enc_v(id) | enc_vl(label) | out_deg | in_deg | rep] (id / label / degree parts optional: NULL leaves them out), count [B]
+ * = the number of those rows.  Backward: drep[v] = dpooled[graph(v), col0 : col0 + H], 0 at dummy rows. */
+int dn_si_pool_sum_f32(int64_t B, const int32_t* node_ptr, const uint8_t* dummy, const int32_t* id, const float* enc_v,
+                       int32_t rows_v, int32_t Kv, const int32_t* label, const float* enc_vl, int32_t rows_vl, int32_t Kvl,
+                       const int32_t* out_deg, const int32_t* in_deg, const float* rep, int32_t H, float* pooled,
+                       int32_t* count, dn_stream_t stream);
+int dn_si_pool_sum_bf16(int64_t B, const int32_t* node_ptr, const uint8_t* dummy, const int32_t* id, const void* enc_v,
+                        int32_t rows_v, int32_t Kv, const int32_t* label, const void* enc_vl, int32_t rows_vl, int32_t Kvl,
+                        const int32_t* out_deg, const int32_t* in_deg, const void* rep, int32_t H, float* pooled,
+                        int32_t* count, dn_stream_t stream);
+int dn_si_pool_sum_bwd_f32(int64_t B, const int32_t* node_ptr, const uint8_t* dummy, const float* dpooled, int32_t D,
+                           int32_t col0, int32_t H, float* drep, dn_stream_t stream);
+int dn_si_pool_sum_bwd_bf16(int64_t B, const int32_t* node_ptr, const uint8_t* dummy, const float* dpooled, int32_t D,
+                            int32_t col0, int32_t H, void* drep, dn_stream_t stream);
+/* Ragged Max head pooling (MaxPredictNet.agg_graph, pred.py:219-236, on the padded masked rows): out [B, C] = max of Y [N, C]
+ * (g_fc applied per row) over the non-dummy rows of graph b, with bias[c] as one more candidate when graph b has fewer of
+ * them than L (a zeroed padded row gives the bias).  argmax [B, C] = the winning row, -1 for the bias; first maximum wins.
+ * Backward: dY[argmax[b, c], c] = dout[b, c] (dY zeroed by the caller). */
+int dn_si_pool_max_f32(int64_t B, const int32_t* node_ptr, const uint8_t* dummy, const float* Y, int32_t C,
+                       const float* bias, int32_t L, float* out, int32_t* argmax, dn_stream_t stream);
+int dn_si_pool_max_bf16(int64_t B, const int32_t* node_ptr, const uint8_t* dummy, const void* Y, int32_t C,
+                        const void* bias, int32_t L, void* out, int32_t* argmax, dn_stream_t stream);
+int dn_si_pool_max_bwd_f32(int64_t B, int32_t C, const int32_t* argmax, const float* dout, float* dY, dn_stream_t stream);
+int dn_si_pool_max_bwd_bf16(int64_t B, int32_t C, const int32_t* argmax, const void* dout, void* dY, dn_stream_t stream);
+/* The padded node mask [B, L] (uint8) of batch_convert_len_to_mask(pre_pad=True) with the dummy positions cleared
+ * (utils/dl.py:113-127, basemodel.py:892-912), in one launch instead of a fill per graph. */
+int dn_si_len_mask_u8(int64_t B, int32_t L, const int32_t* node_ptr, const uint8_t* dummy, uint8_t* mask,
+                      dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
