@@ -138,6 +138,20 @@ _SIGS = {
     "dn_si_pool_max_bwd_f32": (ctypes.c_int, [c_i64, c_i32, P, P, P, P]),
     "dn_si_pool_max_bwd_bf16": (ctypes.c_int, [c_i64, c_i32, P, P, P, P]),
     "dn_si_len_mask_u8": (ctypes.c_int, [c_i64, c_i32, P, P, P, P]),
+    "dn_dual_agg_f32": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, c_i32, P, c_i64, P]),
+    "dn_dual_agg_bf16": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, c_i32, P, c_i64, P]),
+    "dn_dual_agg_bwd_edge_f32": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i32, P, P, P, P, P, P, P, P]),
+    "dn_dual_agg_bwd_edge_bf16": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i32, P, P, P, P, P, P, P, P]),
+    "dn_dual_agg_bwd_node_f32": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, P, c_i64, P]),
+    "dn_dual_agg_bwd_node_bf16": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i32, c_i64, P, P, P, P, P, P, P, P, P, c_i64, P]),
+    "dn_dual_edge_update_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, P, P, P, P, P, P, P, P, P, P, P]),
+    "dn_dual_edge_update_bf16": (ctypes.c_int, [c_i64, c_i64, c_i32, P, P, P, P, P, P, P, P, P, P, P]),
+    "dn_dual_edge_update_bwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, P, P, P, P, P]),
+    "dn_dual_edge_update_bwd_bf16": (ctypes.c_int, [c_i64, c_i64, c_i32, P, P, P, P, P]),
+    "dn_sie_pool_sum_f32": (ctypes.c_int, [c_i64, P, P, P, P, c_i64, P, P, c_i32, c_i32, P, P, c_i32, c_i32, P, P, c_i32, c_i32, P, P, P,
+                                           c_i32, P, P, P]),
+    "dn_sie_pool_sum_bf16": (ctypes.c_int, [c_i64, P, P, P, P, c_i64, P, P, c_i32, c_i32, P, P, c_i32, c_i32, P, P, c_i32, c_i32, P, P, P,
+                                            c_i32, P, P, P]),
 }
 
 _lib = None

@@ -3011,3 +3011,322 @@ def si_len_mask(node_ptr, L, dummy=None):
     launch_tagged("si_len_mask", lambda: check(lib().dn_si_len_mask_u8(B, int(L), ptr(_i32(node_ptr, "node_ptr")), ptr(dummy),
                                                                 ptr(mask.view(torch.uint8)), stream_ptr()), "dn_si_len_mask"))
     return mask
+
+
+def si_read_meta_pair(meta_v, meta_e, need_edges=True):
+    """si_read_meta for a model with node AND edge sides: both metas in ONE device-to-host read.  Returns ((Lp, Lg), (Lpe, Lge)).
+    The edge meta comes from dn_si_filter_meta run on edge_ptr / edge labels (its "id" slot re-checks the label); a graph without
+    edges only raises when need_edges (the edge head would divide by its zero length)."""
+    lp, lg, flags, _, lpe, lge, eflags, _ = torch.cat([meta_v, meta_e]).tolist()
+    if flags:
+        what = "; ".join(m for bit, m in SI_FLAGS if flags & bit)
+        if flags & (4 | 8):
+            raise ValueError("SI model batch: %s" % what)
+        raise _lib.DnHipError("SI model batch: %s" % what)
+    if eflags & (1 | 2):
+        raise _lib.DnHipError("SI model batch: an edge label outside the edge label table")
+    if eflags & 16:
+        raise _lib.DnHipError("SI model batch: inconsistent edge_ptr")
+    if eflags & (4 | 8) and need_edges:
+        raise ValueError("SI model batch: a %s with no edges" % ("pattern" if eflags & 4 else "graph"))
+    return (int(lp), int(lg)), (max(int(lpe), 1), max(int(lge), 1))
+
+
+# ----------------------------------------------------------------------------------------------
+# dual (node + edge) message passing of CompGCN / DMPNN and the ragged edge head (dn_dual.hip)
+# ----------------------------------------------------------------------------------------------
+DUAL_EDGE, DUAL_SUB, DUAL_MULT = 0, 1, 2
+DUAL_MAX_H = 256
+_dual_tls = _threading.local()
+
+
+# The layers' default.  Measured on the scale batch (docs/LAB_NOTES.md "SI count models: CompGCN / DMPNN"): the fused DMPLayer and
+# CompGCNLayer (sub, mult) steps are 7-14 % faster in median than the composed ones, but inside the run-to-run spread of the box, so
+# the composed path stays the default and the fused kernels are an opt-in (`with ops.dual_fused():`).
+DUAL_FUSED_DEFAULT = False
+
+
+def dual_fused_enabled():
+    """Do CompGCNLayer / DMPLayer forwards started NOW on this thread take dn_dual.hip?  The thread's dual_fused / dual_composed
+    override, else ops.DUAL_FUSED_DEFAULT."""
+    m = getattr(_dual_tls, "fused", None)
+    return DUAL_FUSED_DEFAULT if m is None else m
+
+
+class dual_fused:
+    """Context manager: CompGCNLayer (sub, mult) / DMPLayer forwards started inside it (on this thread) run on the fused dual
+    kernels (dn_dual.hip) where the predicate of dual.py allows it.  Their backward passes use the same kernels whenever they run."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_dual_tls, "fused", None)
+        _dual_tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _dual_tls.fused = self.old
+        return False
+
+
+class dual_composed(dual_fused):
+    """Context manager: force the composed path (generic segment kernels + torch glue) for the layers inside it, whatever the
+    default -- for tests and A/B runs.  dual_composed(False) = dual_fused()."""
+
+    def __init__(self, on=True):
+        super().__init__(not on)
+
+
+def dual_supported(*tensors):
+    """The predicate of the fused dual path: fp32 / bf16 rows of one dtype and width H <= 256, contiguous, on the GPU."""
+    t0 = tensors[0]
+    return all(t.is_cuda and t.dim() == 2 and t.dtype == t0.dtype and t.dtype in MFMA_DTYPES and t.is_contiguous()
+               and t.shape[1] == t0.shape[1] for t in tensors) and 1 <= t0.shape[1] <= DUAL_MAX_H
+
+
+class _DualUnits:
+    """Unit table of dn_dual_agg_* over one grouped list of an EdgeIndex ("in": CSR by destination, "out": CSC by source): one
+    unit per segment of at most HUB_SPLIT entries, HUB_SPLIT-entry chunks (with a partial slot each) for the longer ones."""
+
+    def __init__(self, ptr_, num_segments):
+        N, dev = int(num_segments), ptr_.device
+        lo, hi = ptr_[:-1].long(), ptr_[1:].long()
+        nchunk = ((hi - lo + HUB_SPLIT - 1) // HUB_SPLIT).clamp(min=1)
+        first = torch.cat([nchunk.new_zeros(1), torch.cumsum(nchunk, 0)])
+        U = int(first[-1]) if N else 0
+        self.num_units, self.num_slots, self.hub_ids, self.fold_ptr = U, 0, None, None
+        if U == N:
+            seg = torch.arange(N, device=dev)
+            self.units = torch.stack([seg, lo, hi, torch.full_like(seg, -1)], 1).to(I32).contiguous()
+            return
+        seg = torch.repeat_interleave(torch.arange(N, device=dev), nchunk, output_size=U)
+        beg = lo[seg] + (torch.arange(U, device=dev) - first[:-1][seg]) * HUB_SPLIT
+        end = torch.minimum(beg + HUB_SPLIT, hi[seg])
+        hub = (nchunk > 1)[seg]
+        slot = torch.where(hub, torch.cumsum(hub.long(), 0) - 1, torch.full_like(seg, -1))
+        self.units = torch.stack([seg, beg, end, slot], 1).to(I32).contiguous()
+        self.hub_ids = torch.nonzero(nchunk > 1).reshape(-1)
+        hub_chunks = nchunk[self.hub_ids]
+        self.fold_ptr = torch.cat([hub_chunks.new_zeros(1), torch.cumsum(hub_chunks, 0)]).to(I32)
+        self.num_slots = int(self.fold_ptr[-1])
+
+    def part(self, width, device):
+        return torch.empty((self.num_slots, width), dtype=torch.float32, device=device) if self.num_slots else None
+
+    def fold(self, out, part):
+        """out [R, N, H] <- the chunk partials of every long segment summed in chunk order (part [P, R * H] fp32)."""
+        if part is None:
+            return
+        R, _, H = out.shape
+        hub = gather_segsum(part, None, self.fold_ptr)
+        out.index_copy_(1, self.hub_ids, hub.view(-1, R, H).transpose(0, 1).to(out.dtype))
+
+
+def dual_units(index, side):
+    tabs = getattr(index, "_dual_units", None)
+    if tabs is None:
+        tabs = index._dual_units = {}
+    if side not in tabs:
+        tabs[side] = _DualUnits(index.in_ptr if side == "in" else index.out_ptr, index.num_nodes)
+    return tabs[side]
+
+
+def _rev_u8(rev):
+    if rev is None:
+        return None
+    rev = rev.reshape(-1)
+    if rev.dtype == torch.bool:
+        return rev.contiguous().view(torch.uint8)
+    if rev.dtype != torch.uint8:
+        raise _lib.DnHipError("reversed-edge flags must be bool or uint8 on the device (got %s)" % rev.dtype)
+    return rev.contiguous()
+
+
+def dual_agg_raw(mode, ef, x, index, side, rev, scale, out_f32=False):
+    """out [2, N, H] of dn_dual_agg_* over the CSR by destination (side "in": perm = in_perm) or the CSC by source ("out");
+    out_f32: the fp32 sums instead of rows in the dtype of ef."""
+    require_gpu(ef, x, rev, scale)
+    N, E, H = index.num_nodes, index.num_edges, int(ef.shape[1])
+    if ef.shape[0] != E or (x is not None and (x.shape != (N, H) or x.dtype != ef.dtype)) or H > DUAL_MAX_H:
+        raise _lib.DnHipError("dual_agg: ef [E, H], x [N, H] of one dtype and H <= %d expected" % DUAL_MAX_H)
+    if (rev is not None and rev.numel() != E) or (scale is not None and (scale.numel() != E or scale.dtype != torch.float32)):
+        raise _lib.DnHipError("dual_agg: rev uint8 [E] and scale fp32 [E] expected")
+    tab = dual_units(index, side)
+    perm = index.in_perm if side == "in" else index.out_perm
+    out = torch.empty((2, N, H), dtype=torch.float32 if out_f32 else ef.dtype, device=ef.device)
+    part = tab.part(2 * H, ef.device)
+    fn = getattr(lib(), "dn_dual_agg_" + _suffix(ef))
+    launch_tagged("dual_agg", lambda: check(fn(int(mode), N, E, H, tab.num_units, ptr(tab.units), ptr(perm), ptr(index.src), ptr(rev),
+                                               ptr(scale), ptr(ef), ptr(x), ptr(out), 1 if out_f32 else 0, ptr(part), tab.num_slots, stream_ptr()),
+                                            "dn_dual_agg"))
+    tab.fold(out, part)
+    return out
+
+
+class _DualAggFn(torch.autograd.Function):
+    """(out_fwd, out_rev) [N, H] each = sums over the in-edges of v, by direction, of scale_e * m_e (dn_dual_agg_*);
+    backward: d ef on dn_dual_agg_bwd_edge_*, d x (sub / mult) on dn_dual_agg_bwd_node_* over the CSC.  No gradient to scale."""
+
+    @staticmethod
+    def forward(ctx, ef, x, index, rev, scale, mode):
+        ef = ef.contiguous()
+        x = None if mode == DUAL_EDGE else x.contiguous()
+        out = dual_agg_raw(mode, ef, x, index, "in", rev, scale)
+        ctx.index, ctx.mode, ctx.rev, ctx.scale = index, int(mode), rev, scale
+        ctx.save_for_backward(ef if mode == DUAL_MULT else ef.new_empty(0), x if mode == DUAL_MULT else ef.new_empty(0))
+        ctx.shape = (tuple(ef.shape), None if x is None else tuple(x.shape))
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g0, g1):
+        ef, x = ctx.saved_tensors
+        ix, mode, rev, scale = ctx.index, ctx.mode, ctx.rev, ctx.scale
+        N, E = ix.num_nodes, ix.num_edges
+        H = ctx.shape[0][1]
+        ref = g0 if g0 is not None else g1
+        g = torch.stack([t if t is not None else torch.zeros_like(ref) for t in (g0, g1)], 0).contiguous()
+        sfx = _suffix(g)
+        d_ef = d_x = None
+        if ctx.needs_input_grad[0]:
+            d_ef = torch.empty(ctx.shape[0], dtype=g.dtype, device=g.device)
+            fn = getattr(lib(), "dn_dual_agg_bwd_edge_" + sfx)
+            launch_tagged("dual_agg_bwd_edge", lambda: check(fn(mode, N, E, H, ptr(ix.src), ptr(ix.dst), ptr(rev), ptr(scale), ptr(g),
+                                                                ptr(x) if mode == DUAL_MULT else None, ptr(d_ef), stream_ptr()),
+                                                             "dn_dual_agg_bwd_edge"))
+        if mode != DUAL_EDGE and ctx.needs_input_grad[1]:
+            tab = dual_units(ix, "out")
+            dx = torch.empty((1, N, H), dtype=g.dtype, device=g.device)
+            part = tab.part(H, g.device)
+            fn = getattr(lib(), "dn_dual_agg_bwd_node_" + sfx)
+            launch_tagged("dual_agg_bwd_node", lambda: check(fn(mode, N, E, H, tab.num_units, ptr(tab.units), ptr(ix.out_perm), ptr(ix.dst),
+                                                                ptr(rev), ptr(scale), ptr(g), ptr(ef) if mode == DUAL_MULT else None,
+                                                                ptr(dx), ptr(part), tab.num_slots, stream_ptr()),
+                                                             "dn_dual_agg_bwd_node"))
+            tab.fold(dx, part)
+            d_x = dx[0]
+        return d_ef, d_x, None, None, None, None
+
+
+def dual_agg(ef, x, index, rev=None, scale=None, mode=DUAL_EDGE):
+    """(sum over the forward in-edges, sum over the reversed in-edges) of scale_e * m_e per destination node, one pass.
+    mode DUAL_EDGE: m_e = ef_e (x ignored); DUAL_SUB: x[src_e] - ef_e; DUAL_MULT: x[src_e] * ef_e.  rev: bool / uint8 [E] or
+    None (every edge is a forward edge); scale: fp32 [E] in edge order or None."""
+    return _DualAggFn.apply(ef, x, index, _rev_u8(rev), scale, mode)
+
+
+def dmp_coef(index):
+    """2 (1 + log2(1 + out_deg[v])) as fp32 [N] (dmpnn.py:150-157), kept on the index."""
+    c = getattr(index, "_dmp_coef", None)
+    if c is None:
+        out_deg = (index.out_ptr[1:] - index.out_ptr[:-1]).float()
+        c = index._dmp_coef = (2.0 * (1.0 + torch.log2(1.0 + out_deg))).contiguous()
+    return c
+
+
+class _DmpEdgeUpdateFn(torch.autograd.Function):
+    """out[e] = (p_loop[e] + coef[dst_e] p_diff[e]) + (xd[a_e] - xs[b_e]) + ebias  (dn_dual_edge_update_*).  Backward: d p_loop = g,
+    d p_diff = coef[dst] g (dn_dual_edge_update_bwd_*), d xd / d xs = row sums of g from the index's CSR and CSC with the direction
+    flag (two dn_dual_agg_* passes, in-list first, then out-list), d ebias = the column sum."""
+
+    @staticmethod
+    def forward(ctx, p_loop, p_diff, xd, xs, ebias, index, rev):
+        p_loop, p_diff, xd, xs = (t.contiguous() for t in (p_loop, p_diff, xd, xs))
+        require_gpu(p_loop, p_diff, xd, xs, ebias, rev)
+        N, E, H = index.num_nodes, index.num_edges, int(p_loop.shape[1])
+        if p_loop.shape != (E, H) or p_diff.shape != (E, H) or xd.shape != (N, H) or xs.shape != (N, H) or H > DUAL_MAX_H:
+            raise _lib.DnHipError("dmp_edge_update: p_loop / p_diff [E, H], xd / xs [N, H], H <= %d expected" % DUAL_MAX_H)
+        coef = dmp_coef(index)
+        out = torch.empty_like(p_loop)
+        fn = getattr(lib(), "dn_dual_edge_update_" + _suffix(p_loop))
+        launch_tagged("dual_edge_update", lambda: check(fn(N, E, H, ptr(index.src), ptr(index.dst), ptr(rev), ptr(coef), ptr(p_loop),
+                                                           ptr(p_diff), ptr(xd), ptr(xs), ptr(ebias), ptr(out), stream_ptr()),
+                                                        "dn_dual_edge_update"))
+        ctx.index, ctx.rev, ctx.has_bias = index, rev, ebias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        ix, rev = ctx.index, ctx.rev
+        N, E, H = ix.num_nodes, ix.num_edges, int(g.shape[1])
+        d_loop = g if ctx.needs_input_grad[0] else None
+        d_diff = d_xd = d_xs = d_bias = None
+        if ctx.needs_input_grad[1]:
+            d_diff = torch.empty_like(g)
+            fn = getattr(lib(), "dn_dual_edge_update_bwd_" + _suffix(g))
+            launch_tagged("dual_edge_update_bwd", lambda: check(fn(N, E, H, ptr(ix.dst), ptr(dmp_coef(ix)), ptr(g), ptr(d_diff),
+                                                                   stream_ptr()), "dn_dual_edge_update_bwd"))
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            by_dst = dual_agg_raw(DUAL_EDGE, g, None, ix, "in", rev, None, out_f32=True)     # [fwd | rev] sums over the in-lists
+            by_src = dual_agg_raw(DUAL_EDGE, g, None, ix, "out", rev, None, out_f32=True)    # ... over the out-lists
+            # (fp32 sums, rounded ONCE after the two lists are added)
+            d_xd = (by_dst[0] + by_src[1]).to(g.dtype)                            # a_e = dst (forward) | src (reversed)
+            d_xs = (-(by_dst[1] + by_src[0])).to(g.dtype)                         # b_e = src (forward) | dst (reversed)
+        if ctx.has_bias and ctx.needs_input_grad[4]:
+            d_bias = g.float().sum(0).to(g.dtype)
+        return d_loop, d_diff, d_xd, d_xs, d_bias, None, None
+
+
+def dmp_edge_update(p_loop, p_diff, xd, xs, ebias, index, rev=None):
+    return _DmpEdgeUpdateFn.apply(p_loop, p_diff, xd, xs, ebias, index, _rev_u8(rev))
+
+
+class _SiePoolSumFn(torch.autograd.Function):
+    """pooled [B, D] fp32 = per-graph sum of the kept edge head rows (dn_sie_pool_sum_*); the gradient reaches rep only
+    (dn_si_pool_sum_bwd_* on edge_ptr / skip)."""
+
+    @staticmethod
+    def forward(ctx, rep, edge_ptr, skip, src, dst, id_, enc_v, vlabel, enc_vl, elabel, enc_el, out_deg, in_deg):
+        rep = rep.contiguous()
+        require_gpu(rep, edge_ptr, skip, src, dst, id_, enc_v, vlabel, enc_vl, elabel, enc_el, out_deg, in_deg)
+        for t, n in ((edge_ptr, "edge_ptr"), (src, "src"), (dst, "dst"), (id_, "id"), (vlabel, "vlabel"), (elabel, "elabel"),
+                     (out_deg, "out_deg"), (in_deg, "in_deg")):
+            _i32(t, n)
+        B, H = edge_ptr.numel() - 1, rep.shape[1]
+        has_enc = id_ is not None
+        if has_enc and (vlabel is None or elabel is None or any(t.dtype != rep.dtype for t in (enc_v, enc_vl, enc_el))):
+            raise _lib.DnHipError("sie_pool_sum: all three encoder tables, of the dtype of rep, or none")
+        if (has_enc or out_deg is not None) and (src is None or dst is None):
+            raise _lib.DnHipError("sie_pool_sum: the encoder / degree columns need src and dst")
+        if any(t is not None and t.numel() != rep.shape[0] for t in (src, dst, skip, elabel)):
+            raise _lib.DnHipError("sie_pool_sum: one rep row, flag and label per edge expected")
+        N = int(id_.numel()) if has_enc else (int(out_deg.numel()) if out_deg is not None else 0)
+        if has_enc and out_deg is not None and out_deg.numel() != N:
+            raise _lib.DnHipError("sie_pool_sum: id and degrees must cover the same nodes")
+        Kv, Kvl, Kel = (int(enc_v.shape[1]), int(enc_vl.shape[1]), int(enc_el.shape[1])) if has_enc else (0, 0, 0)
+        rows = (int(enc_v.shape[0]), int(enc_vl.shape[0]), int(enc_el.shape[0])) if has_enc else (0, 0, 0)
+        D = 2 * Kv + 2 * Kvl + Kel + (2 if out_deg is not None else 0) + H
+        pooled = torch.empty((B, D), dtype=torch.float32, device=rep.device)
+        count = torch.empty(B, dtype=I32, device=rep.device)
+        fn = getattr(lib(), "dn_sie_pool_sum_" + _suffix(rep))
+        launch_tagged("sie_pool_sum", lambda: check(fn(B, ptr(edge_ptr), ptr(skip), ptr(src), ptr(dst), N, ptr(id_), ptr(enc_v), rows[0], Kv,
+                                                       ptr(vlabel), ptr(enc_vl), rows[1], Kvl, ptr(elabel), ptr(enc_el), rows[2], Kel,
+                                                       ptr(out_deg), ptr(in_deg), ptr(rep), H, ptr(pooled), ptr(count), stream_ptr()),
+                                                    "dn_sie_pool_sum"))
+        ctx.save_for_backward(edge_ptr, skip if skip is not None else edge_ptr.new_empty(0))
+        ctx.has_skip, ctx.shape, ctx.dtype, ctx.col0 = skip is not None, rep.shape, rep.dtype, D - H
+        ctx.mark_non_differentiable(count)
+        return pooled, count
+
+    @staticmethod
+    def backward(ctx, dpooled, _dc):
+        edge_ptr, skip = ctx.saved_tensors
+        if dpooled is None:
+            return (None,) * 13
+        dpooled = dpooled.contiguous().float()
+        B = edge_ptr.numel() - 1
+        drep = torch.empty(ctx.shape, dtype=ctx.dtype, device=dpooled.device)
+        fn = getattr(lib(), "dn_si_pool_sum_bwd_" + _suffix(drep))
+        launch_tagged("sie_pool_sum_bwd", lambda: check(fn(B, ptr(edge_ptr), ptr(skip) if ctx.has_skip else None, ptr(dpooled),
+                                                           int(dpooled.shape[1]), ctx.col0, int(ctx.shape[1]), ptr(drep), stream_ptr()),
+                                                        "dn_si_pool_sum_bwd"))
+        return (drep,) + (None,) * 12
+
+
+def sie_pool_sum(rep, edge_ptr, skip=None, src=None, dst=None, id_=None, enc_v=None, vlabel=None, enc_vl=None, elabel=None,
+                 enc_el=None, out_deg=None, in_deg=None):
+    """(pooled [B, D] fp32, count [B]) over the edges with skip == 0 of every graph; see dn_sie_pool_sum_* (include/dn_hip.h)."""
+    return _SiePoolSumFn.apply(rep, edge_ptr, _u8_or_none(skip), src, dst, id_, enc_v.contiguous() if enc_v is not None else None,
+                               vlabel, enc_vl.contiguous() if enc_vl is not None else None, elabel,
+                               enc_el.contiguous() if enc_el is not None else None, out_deg, in_deg)

@@ -13,6 +13,9 @@ edge id, per-edge scalar = norm x direction mask) and the products run on [N, H]
   DMP       node:  -(sum_{fwd} ef_e) W_in + (sum_{rev} ef_e) W_out + x W_nloop
             edge:  (x W_dst)[a_e] - (x W_src)[b_e] + ef_e W_eloop + 2 (1 + log2(1 + outdeg[dst_e])) ef_e (W_src - W_dst)
                    with (a, b) = (dst, src) on forward edges and (src, dst) on reversed ones
+Both layers also have a fused form on dn_dual.hip (`with ops.dual_fused():`, not the default: it did not measure faster beyond the
+noise, docs/LAB_NOTES.md): CompGCN 'sub' / 'mult' take both direction sums from one pass that composes c_e in registers; DMP takes one
+dual aggregation for the node side, one launch for the edge update, and the row sums of the backward from the cached CSR / CSC.
 GPU only.
 """
 import torch as th
@@ -44,6 +47,14 @@ def _dense(x, w):
     """x @ w with w [in, out]: matrix-core Linear when the width allows it, else rocBLAS."""
     # exact fp32 products here: these layers chain several products through norms and compositions, and are tiny
     return ops.linear_act(x, w.t(), exact=True) if w.shape[0] == w.shape[1] else th.matmul(x, w)
+
+
+def _fused_ok(weight, node_feat, edge_feat):
+    """The fused dual path (dn_dual.hip) applies: asked for (ops.dual_fused), square weights, fp32 / bf16 contiguous
+    rows of one width H <= 256."""
+    return (ops.dual_fused_enabled() and weight.shape[0] == weight.shape[1] and node_feat.dtype == weight.dtype
+            and ops.dual_supported(node_feat, edge_feat) and node_feat.shape[1] == weight.shape[0]
+            and node_feat.shape[0] > 0 and edge_feat.shape[0] > 0)
 
 
 def _degrees(g, ix):
@@ -137,6 +148,13 @@ class CompGCNLayer(nn.Module):
         ix = _edge_index(g)
         scale = self._edge_scale(g, ix)
         rev = g.edata[REVFLAG].reshape(-1).bool() if REVFLAG in g.edata else None
+        if self.comp_opt in ("sub", "mult") and _fused_ok(self.in_weight, node_feat, edge_feat):
+            # both directions from ONE pass over the CSR by destination, composed in registers (dn_dual_agg_*)
+            a_in, a_out = ops.dual_agg(edge_feat, node_feat, ix, rev, scale, ops.DUAL_SUB if self.comp_opt == "sub" else ops.DUAL_MULT)
+            agg = _dense(a_in, self.in_weight)
+            if rev is not None:
+                agg = agg + _dense(a_out, self.out_weight)
+            return self._finish(agg, node_feat, edge_feat)
         ones = th.ones(ix.num_edges, dtype=th.float32, device=node_feat.device) if (scale is None and rev is not None) else None
         base = scale if scale is not None else ones
         parts = [(self.in_weight, base if rev is None else base * (~rev).float())]
@@ -151,6 +169,9 @@ class CompGCNLayer(nn.Module):
                 a = ops.edge_sum(comp, ix, sc)
             t = _dense(a, w)
             agg = t if agg is None else agg + t
+        return self._finish(agg, node_feat, edge_feat)
+
+    def _finish(self, agg, node_feat, edge_feat):
         if self.self_loop:
             out = (agg + _dense(self._comp(node_feat, self.loop_rel), self.loop_weight)) * 0.3333333
         else:
@@ -227,6 +248,8 @@ class DMPLayer(nn.Module):
         if OUTDEGREE not in g.ndata:
             g.ndata[OUTDEGREE] = _degrees(g, ix)[1]
         rev = g.edata[REVFLAG].reshape(-1).bool() if REVFLAG in g.edata else None
+        if _fused_ok(self.in_weight, node_feat, edge_feat):
+            return self._forward_fused(ix, rev, node_feat, edge_feat)
         src, dst = ix.src.long(), ix.dst.long()
         # node side: -(sum_fwd ef) W_in + (sum_rev ef) W_out + x W_nloop
         if rev is None:
@@ -248,6 +271,21 @@ class DMPLayer(nn.Module):
         e = _dense(edge_feat, self.eloop_weight) + add + edge_msg
         if self.ebias is not None:
             e = e + self.ebias
+        return node_out, self.drop(self._run(self.emlp, e))
+
+    def _forward_fused(self, ix, rev, node_feat, edge_feat):
+        """The same layer on dn_dual.hip: both node-side sums from one pass over the CSR by destination, the edge side in one
+        launch that picks (a, b) from the direction flag; the backward's row sums come from the cached CSR / CSC of the index."""
+        a_in, a_out = ops.dual_agg(edge_feat, None, ix, rev, None, ops.DUAL_EDGE)
+        agg = -_dense(a_in, self.in_weight)
+        if rev is not None:
+            agg = _dense(a_out, self.out_weight) + agg
+        h = _dense(node_feat, self.nloop_weight) + agg
+        if self.nbias is not None:
+            h = h + self.nbias
+        node_out = self.drop(self._run(self.nmlp, h))
+        e = ops.dmp_edge_update(_dense(edge_feat, self.eloop_weight), _dense(edge_feat, self.src_weight - self.dst_weight),
+                                _dense(node_feat, self.dst_weight), _dense(node_feat, self.src_weight), self.ebias, ix, rev)
         return node_out, self.drop(self._run(self.emlp, e))
 
     def get_output_dim(self):

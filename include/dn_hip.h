@@ -828,6 +828,69 @@ int dn_si_pool_max_bwd_bf16(int64_t B, int32_t C, const int32_t* argmax, const v
 int dn_si_len_mask_u8(int64_t B, int32_t L, const int32_t* node_ptr, const uint8_t* dummy, uint8_t* mask,
                       dn_stream_t stream);
 
+/* ---- dual (node + edge) message passing of the SI models CompGCN / DMPNN, and the ragged edge head (dn_dual.hip) ----
+ * Dual aggregation, one pass over a grouped edge list (CSR by destination: perm = the edges grouped by dst):
+ *     out[d][v] = sum over e in list(v) with rev_e == d of scale_e * m_e,   d = 0 (forward) | 1 (reversed),  out = [2, N, H]
+ *     m_e = ef_e (DN_DUAL_EDGE) | x[src_e] - ef_e (DN_DUAL_SUB) | x[src_e] * ef_e (DN_DUAL_MULT)
+ * rev (uint8 [E]) and scale (fp32 [E], edge order) may be NULL.  units = int32 [U, 4] records {segment, first entry, end entry,
+ * slot}: slot < 0 = the unit is the whole segment and writes out[.][segment]; slot >= 0 = one chunk of a long segment, its two
+ * fp32 partial rows go to part [P, 2, H] (the caller folds the chunks of a segment in order).  fp32 sums in list order, no
+ * atomics.  out_f32 != 0: out holds the fp32 sums whatever the row dtype (for a caller that adds two passes before it rounds).
+ * Nothing is read outside [0, E) / [0, N): such an entry counts as zero.  H <= 256. */
+#define DN_DUAL_EDGE 0
+#define DN_DUAL_SUB 1
+#define DN_DUAL_MULT 2
+int dn_dual_agg_f32(int32_t mode, int64_t N, int64_t E, int32_t H, int64_t U, const int32_t* units, const int32_t* perm,
+                    const int32_t* src, const uint8_t* rev, const float* scale, const float* ef, const float* x, float* out,
+                    int32_t out_f32, float* part, int64_t P, dn_stream_t stream);
+int dn_dual_agg_bf16(int32_t mode, int64_t N, int64_t E, int32_t H, int64_t U, const int32_t* units, const int32_t* perm,
+                     const int32_t* src, const uint8_t* rev, const float* scale, const void* ef, const void* x, void* out,
+                     int32_t out_f32, float* part, int64_t P, dn_stream_t stream);
+/* Backward, with G_e = scale_e * g[rev_e][dst_e] (g = [2, N, H]):
+ * edge: d_ef[e] = G_e | -G_e | G_e * x[src_e];   node (sub / mult only): dx[u] = sum over the out-list of u (units / perm of
+ * the CSC by source) of G_e | G_e * ef_e, partial rows part [P, H]. */
+int dn_dual_agg_bwd_edge_f32(int32_t mode, int64_t N, int64_t E, int32_t H, const int32_t* src, const int32_t* dst,
+                             const uint8_t* rev, const float* scale, const float* g, const float* x, float* d_ef,
+                             dn_stream_t stream);
+int dn_dual_agg_bwd_edge_bf16(int32_t mode, int64_t N, int64_t E, int32_t H, const int32_t* src, const int32_t* dst,
+                              const uint8_t* rev, const float* scale, const void* g, const void* x, void* d_ef,
+                              dn_stream_t stream);
+int dn_dual_agg_bwd_node_f32(int32_t mode, int64_t N, int64_t E, int32_t H, int64_t U, const int32_t* units,
+                             const int32_t* perm, const int32_t* dst, const uint8_t* rev, const float* scale, const float* g,
+                             const float* ef, float* dx, float* part, int64_t P, dn_stream_t stream);
+int dn_dual_agg_bwd_node_bf16(int32_t mode, int64_t N, int64_t E, int32_t H, int64_t U, const int32_t* units,
+                              const int32_t* perm, const int32_t* dst, const uint8_t* rev, const float* scale, const void* g,
+                              const void* ef, void* dx, float* part, int64_t P, dn_stream_t stream);
+/* DMP edge update (dmpnn.py:111-169): out[e] = (p_loop[e] + coef[dst_e] * p_diff[e]) + (xd[a_e] - xs[b_e]) + ebias with
+ * p_loop = ef W_eloop, p_diff = ef (W_src - W_dst) ([E, H]), xd = x W_dst, xs = x W_src ([N, H]), coef [N] fp32
+ * (= 2 (1 + log2(1 + out_deg))), (a, b) = (dst, src) on forward edges and (src, dst) on reversed ones (rev may be NULL), ebias
+ * [H] or NULL.  Backward piece: d_diff[e] = coef[dst_e] * g[e]. */
+int dn_dual_edge_update_f32(int64_t N, int64_t E, int32_t H, const int32_t* src, const int32_t* dst, const uint8_t* rev,
+                            const float* coef, const float* p_loop, const float* p_diff, const float* xd, const float* xs,
+                            const float* ebias, float* out, dn_stream_t stream);
+int dn_dual_edge_update_bf16(int64_t N, int64_t E, int32_t H, const int32_t* src, const int32_t* dst, const uint8_t* rev,
+                             const float* coef, const void* p_loop, const void* p_diff, const void* xd, const void* xs,
+                             const void* ebias, void* out, dn_stream_t stream);
+int dn_dual_edge_update_bwd_f32(int64_t N, int64_t E, int32_t H, const int32_t* dst, const float* coef, const float* g,
+                                float* d_diff, dn_stream_t stream);
+int dn_dual_edge_update_bwd_bf16(int64_t N, int64_t E, int32_t H, const int32_t* dst, const float* coef, const void* g,
+                                 void* d_diff, dn_stream_t stream);
+/* Ragged Sum / Mean pooling of the edge head rows (basemodel.py:1622-1667): pooled [B, D] fp32 = sum over the edges e = (u, v) of
+ * graph b with skip[e] == 0 (skip = is_dummy | is_reversed, may be NULL) of
+ * [enc_v(id[u]) | enc_v(id[v]) | enc_vl(vlabel[u]) | enc_el(elabel[e]) | enc_vl(vlabel[v]) | out_deg[u] | in_deg[v] | rep[e]]
+ * (the encoder part: all three keys or none; the degree part optional), count [B] = the kept edges.  The backward is
+ * dn_si_pool_sum_bwd_* on edge_ptr and skip. */
+int dn_sie_pool_sum_f32(int64_t B, const int32_t* edge_ptr, const uint8_t* skip, const int32_t* src, const int32_t* dst, int64_t N,
+                        const int32_t* id, const float* enc_v, int32_t rows_v, int32_t Kv, const int32_t* vlabel,
+                        const float* enc_vl, int32_t rows_vl, int32_t Kvl, const int32_t* elabel, const float* enc_el,
+                        int32_t rows_el, int32_t Kel, const int32_t* out_deg, const int32_t* in_deg, const float* rep, int32_t H,
+                        float* pooled, int32_t* count, dn_stream_t stream);
+int dn_sie_pool_sum_bf16(int64_t B, const int32_t* edge_ptr, const uint8_t* skip, const int32_t* src, const int32_t* dst, int64_t N,
+                         const int32_t* id, const void* enc_v, int32_t rows_v, int32_t Kv, const int32_t* vlabel,
+                         const void* enc_vl, int32_t rows_vl, int32_t Kvl, const int32_t* elabel, const void* enc_el,
+                         int32_t rows_el, int32_t Kel, const int32_t* out_deg, const int32_t* in_deg, const void* rep, int32_t H,
+                         float* pooled, int32_t* count, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,635 @@
+"""GPU tests of the SI count models CompGCN / DMPNN (subgraph_isomorphism/graph_adj_v2.py), the fused dual layers (dual.py) and
+their kernels (dn_dual.hip).
+
+* goldens: the reference's own models (tests/golden/si_dual_models*.npz), fp32, in both fp32 arithmetic modes: every OutputDict
+  tensor, every parameter gradient and the gradients of the four rep tensors to RTOL = 1e-4 of the tensor's largest magnitude,
+  masks exact, None patterns identical, BatchNorm buffers after the step (shifts in front of a BatchNorm:
+  si_dual_model_ref.bn_shift);
+* goldens and bit-identical reruns on both layer paths (the composed default and `ops.dual_fused()`);
+* path tags: the new kernels under ops.dual_fused(), the composed layers by default, the padded head only for the
+  weight-returning case, no index build inside a warm fused DMPLayer step;
+* exact-integer tests of the dual aggregation, the DMP edge update and the edge head pooling in fp32 and bf16 (small integer
+  operands, premise asserted: every result is exact whatever the summation order);
+* the fused and the composed (ops.dual_composed) layers against the float64 restatement on one random batch;
+* a scale case: config-3 graphs with reversed and dummy edges, both models at their defaults."""
+import numpy as np
+import pytest
+import torch
+
+import si_dual_model_ref as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+RTOL = 1e-4
+CASES = R.load_golden()
+FORWARD = sorted(n for n in CASES if CASES[n]["forward"])
+
+
+def _run_golden(case):
+    model = R.build_model(case).to(DEV).train()
+    res = model(R.make_graph(R.batch(case, "p"), DEV), R.make_graph(R.batch(case, "g"), DEV))
+    for k in R.REPS:
+        res[k].retain_grad()
+    loss = (res["pred_c"] * R.loss_coef(case["B"], torch.float32, DEV)).sum()
+    for k, c in R.case_coefs(case).items():
+        if res[k] is not None:
+            loss = loss + (res[k] * torch.from_numpy(c).to(DEV)).sum()
+    loss.backward()
+    return model, res
+
+
+@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("name", FORWARD)
+def test_model_matches_the_reference_goldens(name, exact, fused):
+    from dummynode4graphlearning_amd import ops
+    case = CASES[name]
+    a, cfg = case["arrays"], case["cfg"]
+    with ops.f32_exact(exact), ops.dual_fused(fused):
+        model, res = _run_golden(case)
+    assert list(res.keys()) == list(R.OUT_KEYS)
+    assert [k for k in R.OUT_KEYS if res[k] is None] == case["none_out"]
+    bad = []
+
+    def check(tag, got, want):
+        e = R.rel_max(got, want)
+        print("%s %s %s rel_max %.3e" % (name, exact, tag, e))
+        if not e < RTOL:
+            bad.append((tag, e))
+
+    for k in R.OUT_KEYS:
+        if res[k] is None:
+            continue
+        want = a["out/" + k]
+        assert tuple(res[k].shape) == tuple(want.shape), k
+        if res[k].dtype == torch.bool:
+            assert torch.equal(res[k].cpu(), torch.from_numpy(want)), k
+        else:
+            check("out " + k, res[k], want)
+    assert [k for k, p in model.named_parameters() if p.grad is None] == case["none_grad"]
+    for k, p in model.named_parameters():
+        if p.grad is None:
+            continue
+        if R.bn_shift(cfg, k):
+            bound, got = RTOL * R.layer_weight_grad_scale(case, k), float(p.grad.abs().max())
+            print("%s %s grad %s |max| %.3e bound %.3e" % (name, exact, k, got, bound))
+            if not got < bound:
+                bad.append((k, got))
+            continue
+        check("grad " + k, p.grad, a["grad/" + k])
+    assert [k for k in R.REPS if res[k].grad is None] == case["none_rep"]
+    for k in R.REPS:
+        if res[k].grad is not None:
+            check("grad_rep " + k, res[k].grad, a["grad_rep/" + k])
+    sd = model.state_dict()
+    for k in case["buffers"]:
+        if k.endswith("num_batches_tracked"):
+            assert int(sd[k]) == int(a["after/" + case["alias"].get(k, k)]), k
+        else:
+            check("buffer " + k, sd[k], a["after/" + case["alias"].get(k, k)])
+    assert not bad, bad
+
+
+def _tags(fn):
+    from dummynode4graphlearning_amd import ops
+    old = ops.kernel_timer
+    ops.kernel_timer = ops.KernelTimer()
+    try:
+        fn()
+        return set(ops.kernel_timer.summary())
+    finally:
+        ops.kernel_timer = old
+
+
+def _fused_tags(name):
+    from dummynode4graphlearning_amd import ops
+    with ops.dual_fused():
+        return _tags(lambda: _run_golden(CASES[name]))
+
+
+def test_path_tags_show_the_new_kernels_and_the_fallbacks():
+    tags = _fused_tags("dmpnn")
+    for t in ("dual_agg", "dual_agg_bwd_edge", "dual_edge_update", "dual_edge_update_bwd", "sie_pool_sum", "sie_pool_sum_bwd",
+              "si_pool_sum", "si_filter", "si_embed", "si_len_mask"):
+        assert t in tags, (t, tags)
+    assert "si_head_padded" not in tags
+    for name in ("compgcn_mult", "compgcn_sub"):
+        tags = _fused_tags(name)
+        assert {"dual_agg", "dual_agg_bwd_edge", "dual_agg_bwd_node", "sie_pool_sum"} <= tags and "si_head_padded" not in tags
+    tags = _fused_tags("compgcn_corr")
+    assert "dual_agg" not in tags and "sie_pool_sum" in tags                  # corr keeps the composed layer path
+    tags = _tags(lambda: _run_golden(CASES["compgcn_max_head"]))
+    assert {"si_pool_max", "si_pool_max_bwd"} <= tags and "si_head_padded" not in tags and "sie_pool_sum" not in tags
+    tags = _tags(lambda: _run_golden(CASES["compgcn_weights"]))
+    assert "si_head_padded" in tags and "sie_pool_sum" not in tags and "si_pool_sum" not in tags
+    # the layers' default is the composed path (the fused one is an opt-in: it did not measure faster beyond the noise); the
+    # model's own glue kernels run either way
+    from dummynode4graphlearning_amd import ops
+    assert not ops.dual_fused_enabled()
+    import contextlib
+    for cm in (contextlib.nullcontext(), ops.dual_composed(), ops.dual_fused(False)):
+        with cm:
+            tags = _tags(lambda: _run_golden(CASES["dmpnn"]))
+        assert "dual_agg" not in tags and "dual_edge_update" not in tags and {"gather_segsum", "sie_pool_sum", "si_filter"} <= tags
+
+
+def _random_layer_batch(rng, N, E, H, dtype=torch.float32, hub=0):
+    from dummynode4graphlearning_amd import BatchedGraph
+    u, v = rng.integers(0, N, size=E), rng.integers(0, N, size=E)
+    if hub:                                                                   # node 0 becomes a hub on both sides
+        u = np.concatenate([u, np.zeros(hub, np.int64), rng.integers(1, N, size=hub)])
+        v = np.concatenate([v, rng.integers(1, N, size=hub), np.zeros(hub, np.int64)])
+    E = len(u)
+    rev = rng.integers(0, 2, size=E).astype(bool)
+    g = BatchedGraph(torch.from_numpy(u).to(DEV), torch.from_numpy(v).to(DEV), N, edata={"is_reversed": torch.from_numpy(rev).to(DEV)})
+    x = torch.from_numpy(rng.standard_normal((N, H)).astype(np.float32)).to(DEV).to(dtype)
+    ef = torch.from_numpy(rng.standard_normal((E, H)).astype(np.float32)).to(DEV).to(dtype)
+    return g, x, ef, (u, v, rev)
+
+
+def test_warm_dmp_layer_step_builds_no_index():
+    from dummynode4graphlearning_amd import ops
+    from dummynode4graphlearning_amd.subgraph_isomorphism import DMPLayer
+    rng = np.random.default_rng(5)
+    g, x, ef, _ = _random_layer_batch(rng, 300, 1500, 64, hub=100)
+    torch.manual_seed(0)
+    layer = DMPLayer(64, 64).to(DEV)
+
+    def step():
+        xo, eo = layer(g, x.clone().requires_grad_(True), ef.clone().requires_grad_(True))
+        (xo.sum() + eo.sum()).backward()
+
+    with ops.dual_fused():
+        step()                                                                # builds and caches the EdgeIndex and the unit tables
+    calls, real = [], ops.csr_build
+    ops.csr_build = lambda *a, **k: (calls.append(1), real(*a, **k))[1]
+    try:
+        with ops.dual_fused():
+            step()
+        assert not calls, "a warm DMPLayer step grouped the edges again (%d csr_build calls)" % len(calls)
+        with ops.dual_composed():                                             # the composed path does (what the fused path removes)
+            step()
+        assert calls
+    finally:
+        ops.csr_build = real
+
+
+def test_two_runs_are_bit_identical():
+    from dummynode4graphlearning_amd import ops
+    for name, fused in (("dmpnn", True), ("compgcn_mult", True), ("compgcn_norm_both", True), ("dmpnn", False)):
+        outs = []
+        for _ in range(2):
+            with ops.dual_fused(fused):
+                model, res = _run_golden(CASES[name])
+            outs.append([res[k].detach().clone() for k in R.OUT_KEYS if res[k] is not None] +
+                        [res[k].grad.clone() for k in R.REPS if res[k].grad is not None] +
+                        [p.grad.clone() for _, p in model.named_parameters() if p.grad is not None])
+        assert all(torch.equal(x, y) for x, y in zip(*outs)), name
+
+
+def test_bad_batches_raise():
+    from dummynode4graphlearning_amd._lib import DnHipError
+    case = CASES["dmpnn"]
+    model = R.build_model(case).to(DEV)
+    p, g = R.batch(case, "p"), R.batch(case, "g")
+    d = dict(g)
+    d["elabel"] = np.array(d["elabel"], copy=True)
+    d["elabel"][2] = case["cfg"]["max_ngel"]
+    with pytest.raises(DnHipError, match="edge label"):
+        model(R.make_graph(p, DEV), R.make_graph(d, DEV))
+    d = dict(g)
+    d["esizes"] = np.array(d["esizes"], copy=True)
+    d["esizes"][1] += d["esizes"][2]
+    d["esizes"][2] = 0                                                        # graph 2 has no edges
+    with pytest.raises(ValueError, match="no edges"):
+        model(R.make_graph(p, DEV), R.make_graph(d, DEV))
+
+
+# ------------------------------------------------------------------------------------------------ exact-integer kernel tests
+DTYPES = [torch.float32, torch.bfloat16]
+WIDTHS = [16, 64, 128, 256]
+
+
+def _ints(rng, shape, lo, hi, dtype):
+    return torch.from_numpy(rng.integers(lo, hi + 1, size=shape).astype(np.float32)).to(DEV).to(dtype)
+
+
+def _exact_premise(t, dtype):
+    """Every value is an integer the dtype represents exactly (bf16: 8 significant bits -> |v| <= 256; fp32: < 2^24)."""
+    lim = 256 if dtype == torch.bfloat16 else 2 ** 24
+    t = t.double()
+    assert bool((t == t.round()).all()) and float(t.abs().max()) <= lim, float(t.abs().max())
+
+
+def _graph_for_exact(rng, kind, N=40):
+    """(u, v, rev) with a hub at node 0 on both sides; kind: 'below' = hub of exactly HUB_SPLIT entries, 'above' = HUB_SPLIT + 1
+    and a second hub of 2 * HUB_SPLIT + 5, 'allrev' = every edge reversed.  Nodes N - 3 .. N - 1 have no in-edges."""
+    from dummynode4graphlearning_amd import ops
+    S = ops.HUB_SPLIT
+    u, v = list(rng.integers(0, N - 3, size=60)), list(rng.integers(1, N - 3, size=60))
+    v = [int(t) if t != 0 else 1 for t in v]                                  # node 0's in-degree is set below
+    u = [int(t) if t != 0 else 1 for t in u]
+    hub = S + 1 if kind == "above" else S
+    u += list(rng.integers(1, N, size=hub)) + [0] * hub
+    v += [0] * hub + list(rng.integers(1, N - 3, size=hub))
+    if kind == "above":
+        u += list(rng.integers(2, N, size=2 * S + 5))
+        v += [1] * (2 * S + 5)
+    u, v = np.array(u, np.int64), np.array(v, np.int64)
+    rev = np.ones(len(u), bool) if kind == "allrev" else rng.integers(0, 2, size=len(u)).astype(bool)
+    return u, v, rev
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("H", WIDTHS)
+def test_exact_dual_aggregation_forward_and_backward(H, dtype):
+    from dummynode4graphlearning_amd import ops
+    rng = np.random.default_rng(100 + H)
+    N = 40
+    for kind in ("below", "above", "allrev"):
+        u, v, rev = _graph_for_exact(rng, kind, N)
+        E = len(u)
+        ix = ops.EdgeIndex(torch.from_numpy(u).to(DEV), torch.from_numpy(v).to(DEV), N)
+        in_deg = np.bincount(v, minlength=N)
+        assert in_deg[0] == (ops.HUB_SPLIT if kind != "above" else ops.HUB_SPLIT + 1) and (in_deg[N - 3:] == 0).all()
+        ud, vd = torch.from_numpy(u), torch.from_numpy(v)
+        for mode in (ops.DUAL_EDGE, ops.DUAL_SUB, ops.DUAL_MULT):
+            for use_rev in (True, False):
+                for use_scale in (True, False):
+                    # ef in {-1, 0, 1} on every sixth edge, x in {-1, 0, 1} (sub: on every eighth source node only, since
+                    # x - ef is non-zero wherever x is), scale in {1, 2}: over the longest list (2 * HUB_SPLIT + 5 entries)
+                    # |sum| <= 2 * (23 + 133 / 8 + slack) < 256, exact in bf16 too -- the premise is asserted on the float64 result
+                    ef = _ints(rng, (E, H), -1, 1, dtype)
+                    ef[torch.arange(E, device=DEV) % 6 != 0] = 0
+                    x = _ints(rng, (N, H), -1, 1, dtype)
+                    if mode == ops.DUAL_SUB:
+                        x[torch.arange(N, device=DEV) % 8 != 0] = 0
+                    sc = torch.from_numpy(rng.integers(1, 3, size=E).astype(np.float32)).to(DEV) if use_scale else None
+                    if use_scale:
+                        assert bool((sc == 2).any()) and bool((sc == 1).any())
+                    if mode != ops.DUAL_EDGE:
+                        assert bool(x.any())
+                    r = torch.from_numpy(rev).to(DEV) if use_rev else None
+                    ef.requires_grad_(True)
+                    x.requires_grad_(True)
+                    o0, o1 = ops.dual_agg(ef, x, ix, r, sc, mode)
+                    e64, x64 = ef.detach().double().cpu(), x.detach().double().cpu()
+                    m = e64 if mode == ops.DUAL_EDGE else (x64[ud] - e64 if mode == ops.DUAL_SUB else x64[ud] * e64)
+                    s64 = sc.double().cpu().view(-1, 1) if use_scale else torch.ones(E, 1, dtype=torch.float64)
+                    rv = torch.from_numpy(rev if use_rev else np.zeros(E, bool))
+                    w0 = torch.zeros(N, H, dtype=torch.float64).index_add(0, vd[~rv], (s64 * m)[~rv])
+                    w1 = torch.zeros(N, H, dtype=torch.float64).index_add(0, vd[rv], (s64 * m)[rv])
+                    _exact_premise(w0, dtype), _exact_premise(w1, dtype)
+                    assert torch.equal(o0.double().cpu(), w0) and torch.equal(o1.double().cpu(), w1), (kind, mode, use_rev, use_scale)
+                    if not use_rev:
+                        assert not bool(o1.any())
+                    # backward: gradients in {-1, 0, 1} on every fourth node row
+                    g0, g1 = _ints(rng, (N, H), -1, 1, dtype), _ints(rng, (N, H), -1, 1, dtype)
+                    keep = (torch.arange(N, device=DEV) % 4 == 0).view(-1, 1)
+                    g0, g1 = g0 * keep, g1 * keep
+                    torch.autograd.backward([o0, o1], [g0, g1])
+                    G = s64 * torch.where(rv.view(-1, 1), g1.double().cpu()[vd], g0.double().cpu()[vd])
+                    want_ef = G if mode == ops.DUAL_EDGE else (-G if mode == ops.DUAL_SUB else G * x64[ud])
+                    assert torch.equal(ef.grad.double().cpu(), want_ef)
+                    if mode == ops.DUAL_EDGE:
+                        assert x.grad is None
+                    else:
+                        want_x = torch.zeros(N, H, dtype=torch.float64).index_add(0, ud, G if mode == ops.DUAL_SUB else G * e64)
+                        _exact_premise(want_x, dtype)
+                        assert torch.equal(x.grad.double().cpu(), want_x), (kind, mode, use_rev, use_scale)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("H", WIDTHS)
+def test_exact_dmp_edge_update_forward_and_backward(H, dtype):
+    from dummynode4graphlearning_amd import ops
+    rng = np.random.default_rng(200 + H)
+    N = 40
+    for kind in ("below", "above", "allrev"):
+        u, v, rev = _graph_for_exact(rng, kind, N)
+        E = len(u)
+        # out-degrees of 2^k - 1 make coef = 2 (1 + k) an integer; here: coef is replaced by a table of small integers
+        ix = ops.EdgeIndex(torch.from_numpy(u).to(DEV), torch.from_numpy(v).to(DEV), N)
+        ix._dmp_coef = torch.from_numpy(rng.integers(1, 4, size=N).astype(np.float32)).to(DEV)
+        coef = ix._dmp_coef.double().cpu()
+        ud, vd, rv = torch.from_numpy(u), torch.from_numpy(v), torch.from_numpy(rev)
+        for use_rev in (True, False):
+            for use_bias in (True, False):
+                pl, pd = _ints(rng, (E, H), -2, 2, dtype), _ints(rng, (E, H), -2, 2, dtype)
+                xd, xs = _ints(rng, (N, H), -3, 3, dtype), _ints(rng, (N, H), -3, 3, dtype)
+                b = _ints(rng, (H,), -2, 2, dtype) if use_bias else None
+                for t in (pl, pd, xd, xs) + ((b,) if use_bias else ()):
+                    t.requires_grad_(True)
+                out = ops.dmp_edge_update(pl, pd, xd, xs, b, ix, torch.from_numpy(rev).to(DEV) if use_rev else None)
+                r = rv if use_rev else torch.zeros(E, dtype=torch.bool)
+                a_idx, b_idx = torch.where(r, ud, vd), torch.where(r, vd, ud)
+                f = lambda t: t.detach().double().cpu()                       # noqa: E731
+                want = f(pl) + coef[vd].view(-1, 1) * f(pd) + f(xd)[a_idx] - f(xs)[b_idx] + (f(b) if use_bias else 0.0)
+                _exact_premise(want, dtype)
+                assert torch.equal(out.double().cpu(), want), (kind, use_rev, use_bias)
+                g = _ints(rng, (E, H), -1, 1, dtype)
+                g[torch.arange(E, device=DEV) % 3 != 0] = 0                    # row sums over <= 134-entry lists stay <= 256
+                out.backward(g)
+                g64 = f(g)
+                assert torch.equal(f(pl.grad), g64) and torch.equal(f(pd.grad), coef[vd].view(-1, 1) * g64)
+                want_xd = torch.zeros(N, H, dtype=torch.float64).index_add(0, a_idx, g64)
+                want_xs = -torch.zeros(N, H, dtype=torch.float64).index_add(0, b_idx, g64)
+                _exact_premise(want_xd, dtype), _exact_premise(want_xs, dtype)
+                assert torch.equal(f(xd.grad), want_xd) and torch.equal(f(xs.grad), want_xs), (kind, use_rev)
+                if use_bias:
+                    wb = g64.sum(0)
+                    _exact_premise(wb, dtype)
+                    assert torch.equal(f(b.grad), wb)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("H", [16, 64, 128])
+def test_exact_edge_embedding_with_edge_ids(H, dtype):
+    """add_edge_id: emb_el(enc_el[label]) + emb_v(enc_v[id[src]]) + emb_v(enc_v[id[dst]]) and the gradients into both embedding
+    weights (three results into emb_net["v"]), through the model's own key gather and launches."""
+    cfg = dict(CASES["dmpnn_add_ids"]["cfg"], hid_dim=H, max_ngv=32, max_ngel=8)
+    torch.manual_seed(1)
+    model = R.model_class(cfg)(**cfg).to(DEV).to(dtype)
+    assert model.add_edge_id
+    rng = np.random.default_rng(400 + H)
+    N, E = 40, 300
+    ids = torch.from_numpy(rng.integers(0, 32, size=N)).to(DEV).int()
+    u, v = torch.from_numpy(rng.integers(0, N, size=E)).to(DEV).int(), torch.from_numpy(rng.integers(0, N, size=E)).to(DEV).int()
+    el = torch.from_numpy(rng.integers(0, 8, size=E)).to(DEV).int()
+    emb, enc = model.g_emb_net, model.g_enc_net
+    with torch.no_grad():
+        for k in ("v", "el"):
+            emb[k].weight.copy_(_ints(rng, tuple(emb[k].weight.shape), -2, 2, dtype))
+    id_src, id_dst = model._edge_keys(ids, u, v)
+    assert torch.equal(id_src, ids[u.long()]) and torch.equal(id_dst, ids[v.long()])
+    out = model._embed_edges(emb, enc, el, id_src, id_dst)
+    f = lambda t: t.detach().double().cpu()                                   # noqa: E731
+    Ev, Eel, Wv, Wel = f(enc["v"].weight), f(enc["el"].weight), f(emb["v"].weight), f(emb["el"].weight)
+    iu, iv, l = id_src.long().cpu(), id_dst.long().cpu(), el.long().cpu()
+    want = Eel[l] @ Wel + Ev[iu] @ Wv + Ev[iv] @ Wv
+    _exact_premise(want, dtype)
+    assert out.dtype == dtype and torch.equal(f(out), want)
+    G = _ints(rng, (E, H), -1, 1, dtype)
+    G[torch.arange(E, device=DEV) % 3 != 0] = 0                                # 100 non-zero rows: |dW_v| <= 200, exact in bf16
+    out.backward(G)
+    want_el, want_v = Eel[l].t() @ f(G), (Ev[iu] + Ev[iv]).t() @ f(G)
+    _exact_premise(want_el, dtype), _exact_premise(want_v, dtype)
+    assert torch.equal(f(emb["el"].weight.grad), want_el) and torch.equal(f(emb["v"].weight.grad), want_v)
+    assert emb["vl"].weight.grad is None
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("H", WIDTHS)
+def test_exact_edge_head_pooling(H, dtype):
+    from dummynode4graphlearning_amd import ops
+    rng = np.random.default_rng(300 + H)
+    sizes, esizes = [4, 1, 9, 3, 6], [7, 2, 300, 5, 12]                       # graph 1: every edge dropped; graph 2: a long list
+    nptr, eptr = np.concatenate([[0], np.cumsum(sizes)]), np.concatenate([[0], np.cumsum(esizes)])
+    N, E = int(nptr[-1]), int(eptr[-1])
+    u = np.concatenate([rng.integers(0, n, size=m) + o for n, m, o in zip(sizes, esizes, nptr[:-1])])
+    v = np.concatenate([rng.integers(0, n, size=m) + o for n, m, o in zip(sizes, esizes, nptr[:-1])])
+    skip = rng.integers(0, 4, size=E) == 0
+    skip[eptr[1]:eptr[2]] = True
+    ids, vl, el = rng.integers(0, 16, size=N), rng.integers(0, 8, size=N), rng.integers(0, 4, size=E)
+    t32 = lambda a: torch.from_numpy(np.asarray(a)).to(DEV).int()             # noqa: E731
+    enc_v, enc_vl, enc_el = _ints(rng, (16, 8), 0, 1, dtype), _ints(rng, (8, 6), 0, 1, dtype), _ints(rng, (4, 4), 0, 1, dtype)
+    in_deg, out_deg = ops.degrees(t32(u), t32(v), N)
+    seg = torch.repeat_interleave(torch.arange(len(esizes)), torch.from_numpy(np.asarray(esizes)))
+    keep = torch.from_numpy(~skip)
+    ud, vd = torch.from_numpy(u), torch.from_numpy(v)
+    for with_enc, with_deg, with_skip in ((True, True, True), (False, False, True), (True, False, False), (False, True, True)):
+        rep = _ints(rng, (E, H), -1, 1, dtype).requires_grad_(True)
+        enc = (t32(ids), enc_v, t32(vl), enc_vl, t32(el), enc_el) if with_enc else (None,) * 6
+        deg = (out_deg, in_deg) if with_deg else (None, None)
+        S, cnt = ops.sie_pool_sum(rep, t32(eptr), torch.from_numpy(skip).to(DEV) if with_skip else None, t32(u), t32(v), *enc, *deg)
+        f = lambda t: t.detach().double().cpu()                               # noqa: E731
+        parts = []
+        if with_enc:
+            iv, lv = torch.from_numpy(ids), torch.from_numpy(vl)
+            parts += [f(enc_v)[iv[ud]], f(enc_v)[iv[vd]], f(enc_vl)[lv[ud]], f(enc_el)[torch.from_numpy(el)], f(enc_vl)[lv[vd]]]
+        if with_deg:
+            parts += [f(out_deg)[ud].view(-1, 1), f(in_deg)[vd].view(-1, 1)]
+        rows = torch.cat(parts + [f(rep)], 1)
+        k = keep if with_skip else torch.ones(E, dtype=torch.bool)
+        want = torch.zeros(len(esizes), rows.shape[1], dtype=torch.float64).index_add(0, seg[k], rows[k])
+        assert float(want.abs().max()) < 2 ** 24                              # pooled sums are fp32 whatever the row dtype
+        assert S.dtype == torch.float32 and torch.equal(S.double().cpu(), want), (with_enc, with_deg, with_skip)
+        assert cnt.tolist() == torch.zeros(len(esizes), dtype=torch.long).index_add(0, seg[k], torch.ones(int(k.sum()), dtype=torch.long)).tolist()
+        dS = torch.from_numpy(rng.integers(-2, 3, size=tuple(S.shape)).astype(np.float32)).to(DEV)
+        S.backward(dS)
+        want_g = dS.double().cpu()[seg][:, -H:] * k.double().view(-1, 1)
+        assert torch.equal(f(rep.grad), want_g)
+
+
+# ------------------------------------------------------------------------------------------------ layers: fused and composed
+def _layer_params64(layer):
+    return {k: v.detach().double().cpu().requires_grad_(True) for k, v in layer.named_parameters()}
+
+
+@pytest.mark.parametrize("kind", ["dmp", "compgcn_mult", "compgcn_sub"])
+def test_fused_and_composed_layers_match_the_restatement(kind):
+    from dummynode4graphlearning_amd import ops
+    from dummynode4graphlearning_amd.subgraph_isomorphism import CompGCNLayer, DMPLayer
+    from oracle import layers as OL
+    rng = np.random.default_rng(77)
+    H = 64
+    g, x, ef, (u, v, rev) = _random_layer_batch(rng, 200, 900, H, hub=90)
+    torch.manual_seed(3)
+    if kind == "dmp":
+        layer = DMPLayer(H, H, batch_norm=False, act_func="leaky_relu").to(DEV)
+    else:
+        layer = CompGCNLayer(H, H, comp_opt=kind.split("_")[1], edge_norm="both", act_func="leaky_relu").to(DEV)
+    c1 = torch.from_numpy(rng.standard_normal((200, H)).astype(np.float32)).to(DEV)
+    c2 = torch.from_numpy(rng.standard_normal((ef.shape[0], H)).astype(np.float32)).to(DEV)
+    p64 = _layer_params64(layer)
+    x64, e64 = x.double().cpu().requires_grad_(True), ef.double().cpu().requires_grad_(True)
+    ud, vd, rv = torch.from_numpy(u), torch.from_numpy(v), torch.from_numpy(rev)
+    if kind == "dmp":
+        wn, we = OL.dmp_layer(x64, e64, ud, vd, rv, p64, num_mlp_layers=2, act="leaky_relu")
+    else:
+        wn, we = OL.compgcn_layer(x64, e64, ud, vd, rv, p64, comp_opt=kind.split("_")[1], edge_norm="both", act="leaky_relu")
+    ((wn * c1.double().cpu()).sum() + (we * c2.double().cpu()).sum()).backward()
+    for composed in (False, True):
+        layer.zero_grad()
+        xx, ee = x.clone().requires_grad_(True), ef.clone().requires_grad_(True)
+        with ops.f32_exact(True), ops.dual_composed(composed):
+            no, eo = layer(g, xx, ee)
+            ((no * c1).sum() + (eo * c2).sum()).backward()
+        bad = []
+        checks = [("node_out", no, wn), ("edge_out", eo, we), ("grad x", xx.grad, x64.grad), ("grad ef", ee.grad, e64.grad)]
+        checks += [("grad " + k, p.grad, p64[k].grad) for k, p in layer.named_parameters()]
+        for tag, got, want in checks:
+            e = R.rel_max(got, want)
+            print("%s composed=%s %s rel_max %.3e" % (kind, composed, tag, e))
+            if not e < RTOL:
+                bad.append((tag, e))
+        assert not bad, (composed, bad)
+
+
+# ------------------------------------------------------------------------------------------------ scale case
+def scale_batches(seed=0):
+    """config-3 graphs (512 x 49 real nodes) and 512 seeded patterns of 3-9 real nodes, both through
+    bookkeeping.add_reversed_edges (reversed edges: label + max_nel) and transforms.dummy_augment_si.  Returns per side
+    (aug dict of device tensors, numpy view for si_dual_model_ref) and the edge vocabulary the model needs."""
+    from dummynode4graphlearning_amd import synthetic, transforms
+    from dummynode4graphlearning_amd.subgraph_isomorphism import bookkeeping
+    raw = synthetic.config3()
+    vocab = (raw["max_nv"], raw["max_nvl"], raw["max_ne"], raw["max_nel"])
+    rng = np.random.default_rng(seed)
+    G = 512
+    n = rng.integers(3, 10, size=G)
+    m = np.array([int(rng.integers(k, 2 * k + 1)) for k in n])
+    node_ptr, edge_ptr = np.concatenate([[0], np.cumsum(n)]), np.concatenate([[0], np.cumsum(m)])
+    src = np.concatenate([rng.integers(0, k, size=e) + o for k, e, o in zip(n, m, node_ptr[:-1])])
+    dst = np.concatenate([rng.integers(0, k, size=e) + o for k, e, o in zip(n, m, node_ptr[:-1])])
+    pat = dict(node_ptr=node_ptr, edge_ptr=edge_ptr, src=src, dst=dst, node_id=np.concatenate([np.arange(k) for k in n]),
+               node_label=rng.integers(0, raw["max_nvl"], size=int(n.sum())), edge_id=np.concatenate([np.arange(e) for e in m]),
+               edge_label=rng.integers(0, raw["max_nel"], size=int(m.sum())))
+    out, nel = [], 0
+    for b in (pat, raw):
+        t = {k: torch.from_numpy(np.asarray(b[k], np.int64)).to(DEV) for k in
+             ("node_ptr", "edge_ptr", "src", "dst", "node_id", "node_label", "edge_id", "edge_label")}
+        r = bookkeeping.add_reversed_edges(t["edge_ptr"], t["src"], t["dst"], t["edge_id"], t["edge_label"], vocab[2], vocab[3])
+        aug = transforms.dummy_augment_si(t["node_ptr"], r["edge_ptr"], r["src"], r["dst"], t["node_id"], t["node_label"], r["edge_id"],
+                                          r["edge_label"], vocab[0], vocab[1], 2 * vocab[2], 2 * vocab[3], is_reversed=r["is_reversed"])
+        nel = max(nel, int(aug["edge_label"].max()) + 1)
+        view = {"sizes": (aug["node_ptr"][1:] - aug["node_ptr"][:-1]).cpu().numpy(),
+                "esizes": (aug["edge_ptr"][1:] - aug["edge_ptr"][:-1]).cpu().numpy(), "u": aug["src"].cpu().numpy(),
+                "v": aug["dst"].cpu().numpy(), "id": aug["node_id"].cpu().numpy(), "label": aug["node_label"].cpu().numpy(),
+                "elabel": aug["edge_label"].cpu().numpy(), "dummy": aug["is_dummy_node"].bool().cpu().numpy(),
+                "edummy": aug["is_dummy_edge"].bool().cpu().numpy(), "rev": aug["is_reversed"].bool().cpu().numpy()}
+        out.append((aug, view))
+    return out[0], out[1], nel
+
+
+def scale_graph(aug):
+    from dummynode4graphlearning_amd import BatchedGraph
+    N = int(aug["node_label"].numel())
+    return BatchedGraph(aug["src"], aug["dst"], N, batch_num_nodes=(aug["node_ptr"][1:] - aug["node_ptr"][:-1]).long(),
+                        batch_num_edges=(aug["edge_ptr"][1:] - aug["edge_ptr"][:-1]).long(),
+                        ndata={"id": aug["node_id"], "label": aug["node_label"], "is_dummy": aug["is_dummy_node"].bool()},
+                        edata={"label": aug["edge_label"], "is_dummy": aug["is_dummy_edge"].bool(),
+                               "is_reversed": aug["is_reversed"].bool()}, node_ptr=aug["node_ptr"], edge_ptr=aug["edge_ptr"])
+
+
+def scale_cfg(rep_net, nel):
+    return dict(max_ngv=64, max_ngvl=8, max_nge=512, max_ngel=nel, max_npv=64, max_npvl=8, max_npe=512, max_npel=nel, base=2,
+                enc_net="Multihot", emb_net="Orthogonal", filter_net="ScalarFilter", rep_net=rep_net, rep_num_graph_layers=3,
+                rep_num_pattern_layers=3, rep_act_func="leaky_relu", rep_residual=True, share_enc_net=True, share_emb_net=True,
+                share_rep_net=True, pred_net="SumPredictNet", pred_with_enc=True, pred_with_deg=True, hid_dim=64, pred_hid_dim=64,
+                pred_dropout=0.0, rep_dropout=0.0, pred_return_weights="none")
+
+
+def scale_model(cfg, dtype=torch.float32, seed=21):
+    torch.manual_seed(seed)
+    model = R.model_class(cfg)(**cfg)
+    with torch.no_grad():                                      # pred_fc2 starts at zero: perturb so every gradient flows
+        for p in model.parameters():
+            if p.requires_grad:
+                p.add_(0.05 * torch.randn_like(p))
+    return model.to(DEV).to(dtype).train()
+
+
+def _scale_step(model, pg, gg):
+    res = model(pg, gg)
+    for k in R.REPS + ("p_v_emb", "p_e_emb", "g_v_emb", "g_e_emb"):
+        res[k].retain_grad()
+    (res["pred_c"].float() * R.loss_coef(res["pred_c"].shape[0], torch.float32, DEV)).sum().backward()
+    return res
+
+
+@pytest.mark.parametrize("rep_net", ["CompGCN", "DMPNN"])
+def test_scale_fp32_pieces_outside_the_rep_nets_match_the_restatement(rep_net):
+    (pa, p), (ga, g), nel = scale_batches()
+    assert int(ga["node_label"].numel()) == 25600 and len(p["sizes"]) == 512
+    print("scale batch: %d nodes, %d edges" % (ga["node_label"].numel(), ga["src"].numel()))
+    cfg = scale_cfg(rep_net, nel)
+    model = scale_model(cfg)
+    res = _scale_step(model, scale_graph(pa), scale_graph(ga))
+    sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    ref = R.forward(sd, cfg, p, g, reps=[res[k].detach().cpu() for k in R.REPS])
+    checks = [(k, res[k], ref[k]) for k in ("p_v_emb", "p_e_emb", "g_v_emb", "g_e_emb", "pred_c")]
+    for k in ("p_v_mask", "p_e_mask", "g_v_mask", "g_e_mask"):
+        assert torch.equal(res[k].cpu(), ref[k]), k
+    checks += [("grad " + k, res[k].grad, ref["grad_rep"][k]) for k in R.REPS]
+    params = dict(model.named_parameters())
+    checks += [("grad " + k, params[k].grad, ref["grad"][k]) for k in params if k.startswith("pred_net.")]
+    for side, d in (("g", g), ("p", p)):                                      # the embedding weight gradients from the model's own d emb
+        lab, el = torch.from_numpy(np.asarray(d["label"], np.int64)), torch.from_numpy(np.asarray(d["elabel"], np.int64))
+        checks.append(("grad %s_emb_net.vl.weight" % side, params["%s_emb_net.vl.weight" % side].grad,
+                       sd["%s_enc_net.vl.weight" % side].double()[lab].t() @ res[side + "_v_emb"].grad.double().cpu()))
+        checks.append(("grad %s_emb_net.el.weight" % side, params["%s_emb_net.el.weight" % side].grad,
+                       sd["%s_enc_net.el.weight" % side].double()[el].t() @ res[side + "_e_emb"].grad.double().cpu()))
+    bad = []
+    for k, got, want in checks:
+        err = R.rel_max(got, want)
+        print("scale fp32 %s %s rel_max %.3e" % (rep_net, k, err))
+        if not err < RTOL:
+            bad.append((k, err))
+    assert not bad, bad
+
+
+def test_scale_bf16_kernels_match_the_restatement_on_the_same_values():
+    """bf16: each new kernel's output on the scale batch against float64 arithmetic on the same bf16 values, to 2^-8 of the largest
+    magnitude (one bf16 rounding when the result is stored; the pooled sums are fp32)."""
+    from dummynode4graphlearning_amd import ops
+    (pa, p), (ga, g), nel = scale_batches()
+    bound = 2.0 ** -8
+    rng = np.random.default_rng(9)
+    H = 64
+    gg = scale_graph(ga)
+    ix = gg.edge_index()
+    N, E = ix.num_nodes, ix.num_edges
+    bf = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).to(DEV).bfloat16()        # noqa: E731
+    f = lambda t: t.detach().double().cpu()                                                                  # noqa: E731
+    ud, vd, rv = torch.from_numpy(g["u"]), torch.from_numpy(g["v"]), torch.from_numpy(g["rev"])
+    rev = ga["is_reversed"]
+    scale = torch.from_numpy(rng.uniform(0.1, 1.0, size=E).astype(np.float32)).to(DEV)
+    errs = {}
+    x, ef = bf(N, H), bf(E, H)
+    for mode, name in ((ops.DUAL_EDGE, "edge"), (ops.DUAL_SUB, "sub"), (ops.DUAL_MULT, "mult")):
+        xx, ee = x.clone().requires_grad_(True), ef.clone().requires_grad_(True)
+        o0, o1 = ops.dual_agg(ee, xx, ix, rev, scale, mode)
+        m = f(ef) if mode == ops.DUAL_EDGE else (f(x)[ud] - f(ef) if mode == ops.DUAL_SUB else f(x)[ud] * f(ef))
+        m = m * f(scale).view(-1, 1)
+        errs["agg %s fwd" % name] = max(R.rel_max(o0, torch.zeros(N, H, dtype=torch.float64).index_add(0, vd[~rv], m[~rv])),
+                                        R.rel_max(o1, torch.zeros(N, H, dtype=torch.float64).index_add(0, vd[rv], m[rv])))
+        g0, g1 = bf(N, H), bf(N, H)
+        torch.autograd.backward([o0, o1], [g0, g1])
+        G = f(scale).view(-1, 1) * torch.where(rv.view(-1, 1), f(g1)[vd], f(g0)[vd])
+        errs["agg %s d_ef" % name] = R.rel_max(ee.grad, G if mode == ops.DUAL_EDGE else (-G if mode == ops.DUAL_SUB else G * f(x)[ud]))
+        if mode != ops.DUAL_EDGE:
+            errs["agg %s d_x" % name] = R.rel_max(xx.grad, torch.zeros(N, H, dtype=torch.float64).index_add(
+                0, ud, G if mode == ops.DUAL_SUB else G * f(ef)))
+    pl, pd, xd, xs, b = bf(E, H).requires_grad_(True), bf(E, H).requires_grad_(True), bf(N, H).requires_grad_(True), \
+        bf(N, H).requires_grad_(True), bf(H)
+    out = ops.dmp_edge_update(pl, pd, xd, xs, b, ix, rev)
+    coef = f(ops.dmp_coef(ix))
+    want_coef = 2 * (1 + torch.log2(1 + torch.bincount(ud, minlength=N).double()))
+    errs["dmp coef"] = R.rel_max(coef, want_coef)
+    a_idx, b_idx = torch.where(rv, ud, vd), torch.where(rv, vd, ud)
+    errs["edge update fwd"] = R.rel_max(out, f(pl) + coef[vd].view(-1, 1) * f(pd) + f(xd)[a_idx] - f(xs)[b_idx] + f(b))
+    gE = bf(E, H)
+    out.backward(gE)
+    errs["edge update d_diff"] = R.rel_max(pd.grad, coef[vd].view(-1, 1) * f(gE))
+    errs["edge update d_xd"] = R.rel_max(xd.grad, torch.zeros(N, H, dtype=torch.float64).index_add(0, a_idx, f(gE)))
+    errs["edge update d_xs"] = R.rel_max(xs.grad, -torch.zeros(N, H, dtype=torch.float64).index_add(0, b_idx, f(gE)))
+    cfg = scale_cfg("DMPNN", nel)
+    model = scale_model(cfg, torch.bfloat16)
+    sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    rep = bf(E, H).requires_grad_(True)
+    in_deg, out_deg = ops.degrees(ga["src"], ga["dst"], N)
+    skip = (ga["is_dummy_edge"] | ga["is_reversed"])
+    enc = model.g_enc_net
+    S, cnt = ops.sie_pool_sum(rep, ga["edge_ptr"], skip, ga["src"], ga["dst"], ga["node_id"], enc["v"].weight, ga["node_label"],
+                              enc["vl"].weight, ga["edge_label"], enc["el"].weight, out_deg, in_deg)
+    rows = R.edge_rows(sd, cfg, "g", g, f(rep))
+    keep = torch.from_numpy(~R.edge_skip(g))
+    seg = torch.repeat_interleave(torch.arange(len(g["esizes"])), torch.from_numpy(g["esizes"]).long())
+    errs["edge pooled"] = R.rel_max(S, torch.zeros(S.shape, dtype=torch.float64).index_add(0, seg[keep], rows[keep]))
+    assert cnt.tolist() == torch.bincount(seg[keep], minlength=len(g["esizes"])).tolist()
+    for k, e in errs.items():
+        print("scale bf16 %s rel_max %.3e" % (k, e))
+    assert all(e <= bound for e in errs.values()), errs
+    res = _scale_step(model, scale_graph(pa), gg)                              # the whole bf16 model runs and stays finite
+    assert torch.isfinite(res["pred_c"].float()).all()
