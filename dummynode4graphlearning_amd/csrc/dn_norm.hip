@@ -7,7 +7,10 @@
 //
 //   forward   mean[c], var[c] (biased) over rows;  y = (x - mean) * rstd * weight + bias,  rstd = 1 / sqrt(var + eps)
 //   backward  s1[c] = sum dy,  s2[c] = sum dy * xhat;   dx = weight * rstd * (dy - s1 / N - xhat * s2 / N);  dweight = s2, dbias = s1
-// Sums of squares are taken about a per-column shift (row 0) so that a large mean does not cancel the variance away.
+// The forward statistics are (count, mean, M2) per 64-row chunk, each chunk's sums taken about a shift of its own (its first row),
+// merged in a fixed chunk order by Chan's formula (its k-way form): neither a large mean nor a row far from it (a dummy node's row
+// sums a whole graph) cancels the variance away.  (One shift for the whole matrix -- row 0 -- lost the variance when row 0 lay far from the mean:
+// var = s2 / N - d * d is then the difference of two large numbers.)
 #include "dn_common.h"
 #include "../../include/dn_hip.h"
 
@@ -41,7 +44,9 @@ template <> struct V4<bf16_t> {
 };
 
 // One workgroup per chunk of kChunkRows rows: partial[chunk][0][c] = sum_r f(r, c), partial[chunk][1][c] = sum_r g(r, c).
-//   MODE 0 (forward statistics):  f = x - shift,  g = (x - shift)^2        (shift[c] = x[0][c])
+//   MODE 0 (forward statistics):  f = x - shift,  g = (x - shift)^2        (shift[c] = x[first row of the chunk][c]); stored as the
+//                                 chunk's mean = shift + sum f / n and M2 = sum g - (sum f)^2 / n (n = rows of the chunk).  The shift is
+//                                 one of the chunk's rows, so sum g <= n M2: the subtraction loses at most log2(n) = 6 bits
 //   MODE 1 (backward reduction):  f = dy,         g = dy * (x - mean) * rstd      (dy masked by y > 0 when a ReLU is fused)
 template <typename T, int MODE>
 __global__ __launch_bounds__(kBlock) void colreduce_kernel(const T* __restrict__ X, const T* __restrict__ DY,
@@ -56,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void colreduce_kernel(const T* __restrict__
     const int c = lane * 4;
     float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f}, s[4], m[4], rs[4], gw[4], gb[4];
     if (grp < GPB) {
-        if (MODE == 0) V4<T>::load(X + c, s);
+        if (MODE == 0) V4<T>::load(X + (size_t)r0 * C + c, s);
         else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) { m[i] = mean[c + i]; rs[i] = rstd[c + i]; gw[i] = w ? w[c + i] : 1.f; gb[i] = bias ? bias[c + i] : 0.f; }
@@ -84,6 +89,18 @@ __global__ __launch_bounds__(kBlock) void colreduce_kernel(const T* __restrict__
         for (int i = 0; i < 4; ++i) { red[(grp * 2 + 0) * C + c + i] = a[i]; red[(grp * 2 + 1) * C + c + i] = b[i]; }
     }
     __syncthreads();
+    if (MODE == 0) {
+        const int64_t left = N - r0;
+        const float inv = 1.f / (float)(left < kChunkRows ? left : kChunkRows);
+        for (int i = threadIdx.x; i < C; i += kBlock) {
+            float t1 = 0.f, t2 = 0.f;
+            for (int g = 0; g < GPB; ++g) { t1 += red[g * 2 * C + i]; t2 += red[g * 2 * C + C + i]; }       // fixed order
+            const float d = t1 * inv;                                     // the chunk's mean - its shift
+            partial[(size_t)blockIdx.x * 2 * C + i] = (float)X[(size_t)r0 * C + i] + d;
+            partial[(size_t)blockIdx.x * 2 * C + C + i] = fmaxf(fmaf(-t1, d, t2), 0.f);
+        }
+        return;
+    }
     for (int i = threadIdx.x; i < 2 * C; i += kBlock) {
         float t = 0.f;
         for (int g = 0; g < GPB; ++g) t += red[g * 2 * C + i];           // fixed order
@@ -91,19 +108,83 @@ __global__ __launch_bounds__(kBlock) void colreduce_kernel(const T* __restrict__
     }
 }
 
-// combine the chunk partials: 8 threads share a column (thread `slice` adds chunks slice, slice + 8, ... with 4 loads in flight),
-// the 8 slice sums are folded in slice order -- a fixed association, so the result is reproducible; a single thread walking a few
-// hundred partials is a 40 us latency chain.  MODE 0: mean / var / rstd;  MODE 1: s1, s2 as they are
-template <int MODE, typename T>
-__global__ __launch_bounds__(kBlock) void colfinal_kernel(const float* __restrict__ partial, int64_t nchunks, int64_t N, int32_t C,
-                                                          const T* __restrict__ X, float eps, float* __restrict__ out0,
-                                                          float* __restrict__ out1, float* __restrict__ out2,
-                                                          float* __restrict__ run_mean, float* __restrict__ run_var,
-                                                          float momentum, long long* __restrict__ batches_tracked) {
-    constexpr int SL = 8, CPB = kBlock / SL;                            // 32 columns per block
-    __shared__ float r1[SL][CPB], r2[SL][CPB];
-    const int cl = threadIdx.x % CPB, slice = threadIdx.x / CPB;
-    const int c = blockIdx.x * CPB + cl;
+// The two combines of the chunk partials share one shape: 8 threads share a column (thread `slice` takes chunks slice, slice + 8, ...
+// with 4 loads in flight), the 8 slice results are folded in slice order -- a fixed association, so the result is reproducible; a
+// single thread walking a few hundred partials is a 40 us latency chain.
+constexpr int kSlices = 8, kColsPerBlock = kBlock / kSlices;            // 32 columns per block
+
+// forward: the partials are the chunks' (mean_k, M2_k) over n_k rows -> mean / var / rstd (+ the running statistics).  Chan's merge in
+// its k-way form:  mean = sum n_k mean_k / N,  M2 = sum M2_k + sum n_k (mean_k - mean)^2  -- every term of M2 is >= 0, nothing
+// cancels.  The means are summed about chunk 0's (a typical value: what an outlying row moves it by is divided by its 64 rows); every
+// thread of a column folds the slices' sums alike, so all 8 hold the same mean for the second walk.
+__global__ __launch_bounds__(kBlock) void colstats_kernel(const float* __restrict__ partial, int64_t nchunks, int64_t N, int32_t C,
+                                                          float eps, float* __restrict__ mean_out, float* __restrict__ var_out,
+                                                          float* __restrict__ rstd_out, float* __restrict__ run_mean,
+                                                          float* __restrict__ run_var, float momentum,
+                                                          long long* __restrict__ batches_tracked) {
+    constexpr int SL = kSlices;
+    __shared__ float r1[SL][kColsPerBlock], r2[SL][kColsPerBlock];
+    const int cl = threadIdx.x % kColsPerBlock, slice = threadIdx.x / kColsPerBlock;
+    const int c = blockIdx.x * kColsPerBlock + cl;
+    const bool live = c < C;                                            // (idle columns still meet both barriers)
+    auto rows_of = [&](int64_t k) { const int64_t left = N - k * kChunkRows; return (float)(left < kChunkRows ? left : kChunkRows); };
+    auto mean_of = [&](int64_t k) { return partial[(size_t)k * 2 * C + c]; };
+    auto m2_of = [&](int64_t k) { return partial[(size_t)k * 2 * C + C + c]; };
+    const float ref = live ? mean_of(0) : 0.f;                          // (nchunks >= 1: N >= 1)
+    float s1 = 0.f, s2 = 0.f;
+    if (live) {
+        int64_t k = slice;
+        for (; k + 3 * SL < nchunks; k += 4 * SL) {
+            const float a0 = mean_of(k), a1 = mean_of(k + SL), a2 = mean_of(k + 2 * SL), a3 = mean_of(k + 3 * SL);
+            s1 = fmaf(rows_of(k), a0 - ref, s1); s1 = fmaf(rows_of(k + SL), a1 - ref, s1);
+            s1 = fmaf(rows_of(k + 2 * SL), a2 - ref, s1); s1 = fmaf(rows_of(k + 3 * SL), a3 - ref, s1);
+        }
+        for (; k < nchunks; k += SL) s1 = fmaf(rows_of(k), mean_of(k) - ref, s1);
+    }
+    r1[slice][cl] = s1;
+    __syncthreads();
+    s1 = r1[0][cl];
+#pragma unroll
+    for (int j = 1; j < SL; ++j) s1 += r1[j][cl];
+    const float mean = ref + s1 / (float)N;
+    if (live) {
+        int64_t k = slice;
+        for (; k + 3 * SL < nchunks; k += 4 * SL) {
+            const float a0 = mean_of(k) - mean, a1 = mean_of(k + SL) - mean, a2 = mean_of(k + 2 * SL) - mean, a3 = mean_of(k + 3 * SL) - mean;
+            const float b0 = m2_of(k), b1 = m2_of(k + SL), b2 = m2_of(k + 2 * SL), b3 = m2_of(k + 3 * SL);
+            s2 += fmaf(rows_of(k) * a0, a0, b0); s2 += fmaf(rows_of(k + SL) * a1, a1, b1);
+            s2 += fmaf(rows_of(k + 2 * SL) * a2, a2, b2); s2 += fmaf(rows_of(k + 3 * SL) * a3, a3, b3);
+        }
+        for (; k < nchunks; k += SL) {
+            const float a0 = mean_of(k) - mean;
+            s2 += fmaf(rows_of(k) * a0, a0, m2_of(k));
+        }
+    }
+    r2[slice][cl] = s2;
+    __syncthreads();
+    if (slice != 0 || !live) return;
+    s2 = r2[0][cl];
+#pragma unroll
+    for (int j = 1; j < SL; ++j) s2 += r2[j][cl];
+    const float var = fmaxf(s2 / (float)N, 0.f);
+    mean_out[c] = mean;
+    var_out[c] = var;
+    rstd_out[c] = rsqrtf(var + eps);
+    if (batches_tracked && c == 0) *batches_tracked += 1;              // (BatchNorm's num_batches_tracked buffer: no launch of its own)
+    if (run_mean) {                                                     // torch's update: r = (1 - m) r + m * new, unbiased variance
+        const float unb = var * ((float)N / (float)(N > 1 ? N - 1 : 1));
+        run_mean[c] = run_mean[c] * (1.f - momentum) + momentum * mean;
+        run_var[c] = run_var[c] * (1.f - momentum) + momentum * unb;
+    }
+}
+
+// backward: the partials are plain sums -> s1[c] = sum dy, s2[c] = sum dy * xhat
+__global__ __launch_bounds__(kBlock) void colsums_kernel(const float* __restrict__ partial, int64_t nchunks, int32_t C,
+                                                         float* __restrict__ out1, float* __restrict__ out2) {
+    constexpr int SL = kSlices;
+    __shared__ float r1[SL][kColsPerBlock], r2[SL][kColsPerBlock];
+    const int cl = threadIdx.x % kColsPerBlock, slice = threadIdx.x / kColsPerBlock;
+    const int c = blockIdx.x * kColsPerBlock + cl;
     float s1 = 0.f, s2 = 0.f;
     if (c < C) {
         int64_t k = slice;
@@ -128,24 +209,8 @@ __global__ __launch_bounds__(kBlock) void colfinal_kernel(const float* __restric
     s2 = r2[0][cl];
 #pragma unroll
     for (int j = 1; j < SL; ++j) { s1 += r1[j][cl]; s2 += r2[j][cl]; }
-    if (MODE == 0) {
-        const float inv = 1.f / (float)N;
-        const float d = s1 * inv;                                       // mean - shift
-        const float var = fmaxf(s2 * inv - d * d, 0.f);
-        const float mean = (float)X[c] + d;
-        out0[c] = mean;
-        out1[c] = var;
-        out2[c] = rsqrtf(var + eps);
-        if (batches_tracked && c == 0) *batches_tracked += 1;          // (BatchNorm's num_batches_tracked buffer: no launch of its own)
-        if (run_mean) {                                                 // torch's update: r = (1 - m) r + m * new, unbiased variance
-            const float unb = var * ((float)N / (float)(N > 1 ? N - 1 : 1));
-            run_mean[c] = run_mean[c] * (1.f - momentum) + momentum * mean;
-            run_var[c] = run_var[c] * (1.f - momentum) + momentum * unb;
-        }
-    } else {
-        out0[c] = s1;
-        out1[c] = s2;
-    }
+    out1[c] = s1;
+    out2[c] = s2;
 }
 
 // MODE 0: y = relu?((x - mean) * rstd * w + b);   MODE 1: dx = w * rstd * (dy' - s1 / N - xhat * s2 / N), dy' = dy masked by y > 0
@@ -230,8 +295,8 @@ int bn_forward(const T* X, int64_t N, int32_t C, const float* w, const float* b,
     DN_REQUIRE(GPB >= 1, "dn_batchnorm_rows: C too large");
     hipLaunchKernelGGL((colreduce_kernel<T, 0>), dim3((unsigned)nchunks), dim3(kBlock), (size_t)GPB * 2 * C * sizeof(float), st, X,
                        (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, N, C, ws);
-    hipLaunchKernelGGL((colfinal_kernel<0, T>), dim3((unsigned)dn_cdiv(C, kBlock / 8)), dim3(kBlock), 0, st, (const float*)ws, nchunks, N, C, X,
-                       eps, mean, var, rstd, run_mean, run_var, momentum, batches_tracked);
+    hipLaunchKernelGGL(colstats_kernel, dim3((unsigned)dn_cdiv(C, kColsPerBlock)), dim3(kBlock), 0, st, (const float*)ws, nchunks, N, C, eps,
+                       mean, var, rstd, run_mean, run_var, momentum, batches_tracked);
     const int64_t blocks = dn_cdiv(N * (C / 4), kBlock);
     const int32_t cvec = ((reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(rstd) | reinterpret_cast<uintptr_t>(w) |
                            reinterpret_cast<uintptr_t>(b)) % 16) == 0;
@@ -254,8 +319,7 @@ int bn_backward(const T* DY, const T* X, int64_t N, int32_t C, const float* mean
     const int GPB = kBlock / (C / 4);
     hipLaunchKernelGGL((colreduce_kernel<T, 1>), dim3((unsigned)nchunks), dim3(kBlock), (size_t)GPB * 2 * C * sizeof(float), st, X, DY, mean,
                        rstd, w, b, relu, N, C, ws);
-    hipLaunchKernelGGL((colfinal_kernel<1, T>), dim3((unsigned)dn_cdiv(C, kBlock / 8)), dim3(kBlock), 0, st, (const float*)ws, nchunks, N, C, X,
-                       0.f, s1, s2, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, (long long*)nullptr);
+    hipLaunchKernelGGL(colsums_kernel, dim3((unsigned)dn_cdiv(C, kColsPerBlock)), dim3(kBlock), 0, st, (const float*)ws, nchunks, C, s1, s2);
     const int64_t blocks = dn_cdiv(N * (C / 4), kBlock);
     const int32_t cvec = ((reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(rstd) | reinterpret_cast<uintptr_t>(w) |
                            reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(s2)) % 16) == 0;

@@ -76,6 +76,8 @@ def gather_segsum(x, idx=None, ptr_=None, num_segments=None, scale=None, self_in
     require_gpu(x, idx, ptr_, scale, self_in, out)
     assert x.dim() == 2
     _i32(idx, "idx"), _i32(ptr_, "ptr")
+    # (the launch reads x.data_ptr() with x.shape[1] as the row stride and walks idx / ptr / scale / self_in element by element:
+    #  require_gpu refuses a strided view -- x_wide[:, :H], idx[::2] -- that would be read as garbage)
     H = x.shape[1]
     M = idx.numel() if idx is not None else (x.shape[0] if ptr_ is None else None)
     if ptr_ is not None:
@@ -1130,7 +1132,10 @@ def gather_rows(x, idx, csr=None):
 def edge_dot(a, ia, b, ib):
     """out[e] = <a[ia[e]], b[ib[e]]>  (dn_edge_dot_*), fp32."""
     require_gpu(a, ia, b, ib)
+    assert a.dim() == 2 and b.dim() == 2 and a.shape[1] == b.shape[1] and a.dtype == b.dtype
+    _i32(ia, "ia"), _i32(ib, "ib")
     E = ia.numel() if ia is not None else a.shape[0]
+    assert (ib.numel() == E) if ib is not None else (b.shape[0] >= E)
     out = torch.empty(E, dtype=torch.float32, device=a.device)
     check(getattr(lib(), "dn_edge_dot_" + _suffix(a))(ptr(a), ptr(ia), ptr(b), ptr(ib), a.shape[1], E, ptr(out), stream_ptr()),
           "dn_edge_dot")

@@ -428,6 +428,29 @@ def test_edge_dot_and_neighbor_max(dtype, H):
     torch.testing.assert_close(xd.grad.cpu().double().sum(0), xr.grad.sum(0), rtol=tol, atol=tol * 10)
     if dtype == torch.float32:
         torch.testing.assert_close(xd.grad.cpu().double(), xr.grad, rtol=1e-5, atol=1e-5)
+    else:
+        # bf16: the full gradient on an input WITHOUT ties -- every destination's list gathers distinct bf16 values in every column (a
+        # per-column permutation of 256 distinct bf16 numbers, simple edges), so the arg-max source is unambiguous and a gradient entry
+        # routed to the wrong source row shows (a column sum does not change when it is)
+        pair = np.unique(np.stack([src, dst], 1), axis=0)
+        s2, d2 = pair[:, 0], pair[:, 1]
+        vals = torch.arange(-128, 128, dtype=torch.float32) / 8.0                       # 256 distinct values, each exact in bf16
+        N2 = 256
+        keep = (s2 < N2) & (d2 < N2)
+        s2, d2 = s2[keep], d2[keep]
+        x2 = torch.stack([vals[torch.from_numpy(rng.permutation(N2))] for _ in range(H)], 1).to(dtype)
+        assert torch.equal(x2.float().sort(0).values, vals.view(-1, 1).expand(N2, H))    # distinct per column: no ties anywhere
+        index2 = ops.EdgeIndex(torch.from_numpy(s2).to(DEV, torch.int32), torch.from_numpy(d2).to(DEV, torch.int32), N2)
+        x2d = x2.to(DEV).requires_grad_(True)
+        out2 = ops.neighbor_max(x2d, index2)
+        out2.backward(g[:N2].to(DEV))
+        x2r = x2.double().requires_grad_(True)
+        want2 = OL.sage_conv(x2r, torch.from_numpy(s2), torch.from_numpy(d2), torch.eye(H, dtype=torch.float64), None,
+                             torch.zeros(H, H, dtype=torch.float64), aggr="max")
+        want2.backward(g[:N2].double())
+        torch.testing.assert_close(out2.detach().cpu().double(), want2.detach(), rtol=0, atol=0)
+        # (a source's gradient row sums the upstream entries of the destinations it wins, in fp32, rounded once to bf16)
+        torch.testing.assert_close(x2d.grad.cpu().double(), x2r.grad, rtol=2 ** -8, atol=1e-6)
 
 
 @pytest.mark.parametrize("tiles_per_wg", [1, 2, 3, 4, 7, 8, 9, 17])
@@ -776,27 +799,37 @@ def test_batch_norm_rows_matches_torch(N, C, dt):
     output, batch statistics, input / weight / bias gradients; a large column mean must not cancel the variance away."""
     ops = _ops()
     rng = np.random.default_rng(N + C)
-    x = torch.from_numpy((rng.standard_normal((N, C)) * 2.0 + 30.0 * rng.standard_normal(C)).astype(np.float32)).to(dt)
+    x0 = rng.standard_normal((N, C)) * 2.0 + 30.0 * rng.standard_normal(C)
     w = torch.from_numpy(rng.standard_normal(C).astype(np.float32)).to(dt)
     b = torch.from_numpy(rng.standard_normal(C).astype(np.float32)).to(dt)
     coef = torch.from_numpy(rng.standard_normal((N, C)).astype(np.float32)).to(dt)
-    xd, wd, bd = (t.to(DEV).requires_grad_(True) for t in (x, w, b))
-    y, mean, var = ops.batch_norm_rows(xd, wd, bd, 1e-5)
-    y.backward(coef.to(DEV))
-    xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))
-    yr = torch.nn.functional.batch_norm(xr, None, None, wr, br, training=True, eps=1e-5)
-    yr.backward(coef.double())
-    tol = dict(rtol=2e-2, atol=6e-2) if dt == torch.bfloat16 else dict(rtol=2e-4, atol=2e-4)
-    torch.testing.assert_close(mean.cpu().double(), x.double().mean(0), rtol=1e-5, atol=1e-4)
-    torch.testing.assert_close(var.cpu().double(), x.double().var(0, unbiased=False), rtol=2e-4, atol=1e-5)
-    torch.testing.assert_close(y.detach().cpu().double(), yr.detach(), **tol)
-    if N > 1:
-        gt = dict(rtol=3e-2, atol=0.15) if dt == torch.bfloat16 else dict(rtol=1e-3, atol=1e-3)
-        torch.testing.assert_close(xd.grad.cpu().double(), xr.grad, **gt)
-        torch.testing.assert_close(wd.grad.cpu().double(), wr.grad, rtol=3e-2 if dt == torch.bfloat16 else 1e-3,
-                                   atol=(0.5 if dt == torch.bfloat16 else 1e-3) * max(1.0, N ** 0.5 / 10))
-        torch.testing.assert_close(bd.grad.cpu().double(), br.grad, rtol=3e-2 if dt == torch.bfloat16 else 1e-4,
-                                   atol=(0.5 if dt == torch.bfloat16 else 1e-3) * max(1.0, N ** 0.5 / 10))
+    # the same draw again with row 0 moved K standard deviations off the column mean (a dummy node's row sums a whole graph: nothing says
+    # row 0 is typical), column 0 constant except for row 0 -- at the same tolerances.  (Statistics taken about row 0 as the one shift
+    # lost the variance there: var = s2 / N - d * d cancels.)
+    outliers = (0, 30, 300, 1000) if (N, C) in ((5000, 128), (20181, 256), (300, 40)) else (0,)
+    for K in outliers:
+        xk = x0.copy()
+        if K:
+            xk[0] = x0.mean(0) + K * 2.0
+            xk[1:, 0] = x0[1, 0]
+        x = torch.from_numpy(xk.astype(np.float32)).to(dt)
+        xd, wd, bd = (t.to(DEV).requires_grad_(True) for t in (x, w, b))
+        y, mean, var = ops.batch_norm_rows(xd, wd, bd, 1e-5)
+        y.backward(coef.to(DEV))
+        xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))
+        yr = torch.nn.functional.batch_norm(xr, None, None, wr, br, training=True, eps=1e-5)
+        yr.backward(coef.double())
+        tol = dict(rtol=2e-2, atol=6e-2) if dt == torch.bfloat16 else dict(rtol=2e-4, atol=2e-4)
+        torch.testing.assert_close(mean.cpu().double(), x.double().mean(0), rtol=1e-5, atol=1e-4)
+        torch.testing.assert_close(var.cpu().double(), x.double().var(0, unbiased=False), rtol=2e-4, atol=1e-5)
+        torch.testing.assert_close(y.detach().cpu().double(), yr.detach(), **tol)
+        if N > 1:
+            gt = dict(rtol=3e-2, atol=0.15) if dt == torch.bfloat16 else dict(rtol=1e-3, atol=1e-3)
+            torch.testing.assert_close(xd.grad.cpu().double(), xr.grad, **gt)
+            torch.testing.assert_close(wd.grad.cpu().double(), wr.grad, rtol=3e-2 if dt == torch.bfloat16 else 1e-3,
+                                       atol=(0.5 if dt == torch.bfloat16 else 1e-3) * max(1.0, N ** 0.5 / 10))
+            torch.testing.assert_close(bd.grad.cpu().double(), br.grad, rtol=3e-2 if dt == torch.bfloat16 else 1e-4,
+                                       atol=(0.5 if dt == torch.bfloat16 else 1e-3) * max(1.0, N ** 0.5 / 10))
 
 
 @pytest.mark.parametrize("N,C", [(63, 4), (5000, 128), (20181, 256)])
