@@ -19,6 +19,11 @@ int launch_chain2_ring256(const void* X, const void* W1n, const void* b1, const 
                           const void* mask0, const void* mask1, int64_t N, void* Y1, void* Y2, void* bits1, void* bits2,
                           float slope, hipStream_t st);
 
+// dn_rel.hip: the fixed-order sum of a weight-gradient launch's chunk partials (wgrad_reduce_kernel) on a workspace laid out as
+// dn_rows_wgrad_bf16 leaves it -- [num_chunks][H * H] tiles, then [num_chunks][H] column sums (with_colsum).
+int launch_wgrad_reduce(const float* workspace, const int32_t* chunk_ptr, int64_t num_chunks, int32_t H, int64_t R, void* out,
+                        int32_t out_is_f32, bool with_colsum, float* out_colsum, void* out_colsum_lp, hipStream_t st);
+
 // ---- the per-batch index as ONE call (dn_conv_index.hip: dn_conv_index_build_i32) -- the builders' launches without their host sides
 constexpr int kRilPlanWords = 14;      // ril_plan's 12 words behind the 5 + 2 R + 4 meta words of the graph-local row index, then the
                                        // largest graph's nodes and edges (ril_fill_kernel)

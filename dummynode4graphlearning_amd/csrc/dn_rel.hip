@@ -2121,6 +2121,27 @@ __global__ __launch_bounds__(H * 4) void fold_tail_kernel(const float* __restric
 
 }  // namespace
 
+namespace dn_internal {
+
+// wgrad_reduce_kernel on a workspace laid out as dn_rows_wgrad_bf16 leaves it: [num_chunks][H * H] partial tiles, then
+// [num_chunks][H] column-sum partials (with_colsum).  For the launchers of other translation units (dn_mlp_bwd.hip).
+int launch_wgrad_reduce(const float* workspace, const int32_t* chunk_ptr, int64_t num_chunks, int32_t H, int64_t R, void* out,
+                        int32_t out_is_f32, bool with_colsum, float* out_colsum, void* out_colsum_lp, hipStream_t st) {
+    const int64_t tile = (int64_t)H * H;
+    const float* csp = with_colsum ? workspace + (size_t)num_chunks * tile : nullptr;
+    dim3 grid((unsigned)(dn_cdiv(tile, 128) + (csp ? dn_cdiv(H, 128) : 0)), (unsigned)R);
+    if (out_is_f32)
+        hipLaunchKernelGGL((wgrad_reduce_kernel<float>), grid, dim3(256), 0, st, workspace, chunk_ptr, tile, (float*)out, csp, H,
+                           out_colsum, (float*)out_colsum_lp);
+    else
+        hipLaunchKernelGGL((wgrad_reduce_kernel<bf16_t>), grid, dim3(256), 0, st, workspace, chunk_ptr, tile, (bf16_t*)out, csp, H,
+                           out_colsum, (bf16_t*)out_colsum_lp);
+    DN_CHECK_LAUNCH();
+    return DN_OK;
+}
+
+}  // namespace dn_internal
+
 extern "C" {
 
 int dn_fold_tail_bf16(const float* part, const int32_t* part_ptr, int64_t num_segments, int32_t H, const void* Wn,

@@ -2265,14 +2265,61 @@ def relu_bwd(g, y, slope=0.0):
     return out
 
 
+# DN_MLP_BWD_FUSED=0: the bf16 two-layer MLP at H = 256 keeps its three backward launches (weight gradient 2, the input-gradient chain,
+# weight gradient 1) instead of dn_mlp_bwd_fused_bf16 twice -- for A/B runs and for tracing (results are bit-identical either way)
+MLP_BWD_FUSED_ENABLED = _os.environ.get("DN_MLP_BWD_FUSED", "1") != "0"
+# ... from this many rows on.  Smaller batches keep the three launches: the fused launches were built for and measured on the
+# HBM-bound whole batch (1 M rows: step 3.18 -> 3.08 ms); an H = 256 layer on a small batch is _RginLayerWideFn's (one weight-gradient
+# launch for the whole layer), and where that is switched off its separate functions stay what they were
+MLP_BWD_FUSED_MIN_ROWS = int(_os.environ.get("DN_MLP_BWD_FUSED_MIN_ROWS", str(1 << 18)))
+
+
+def mlp_bwd_fused_supported(g, a, w):
+    return (g.dtype == torch.bfloat16 and a.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and g.dim() == 2
+            and g.shape[0] > 0 and g.shape[1] == 256 and a.shape == g.shape and tuple(w.shape) == (256, 256))
+
+
+def mlp_bwd_fused(g, a, w, chunk_table, mask_in_bits=None, mask_out_bits=None, slope=0.0):
+    """One Linear's backward in one pass over its rows (dn_mlp_bwd_fused_bf16, bf16, H = 256): with gm = g masked by mask_in_bits,
+    returns (gw = gm^T a [H, H], gb = colsum(gm) [H], g_next = gm @ w masked by mask_out_bits [N, H]).  w: Linear.weight as stored
+    ([out, in]); masks: the uint8 [N, H/8] bit tensors of rows_chain2 (both or neither); chunk_table: a one-relation row-chunk table
+    over the N rows (_dense_table).  Bit-identical to rows_wgrad (mask_a_bits) + rows_chain2 (w_kn) + rows_wgrad on the same table."""
+    chunks, chunk_ptr, nchunks = chunk_table
+    g, a, w = g.contiguous(), a.contiguous(), w.contiguous()
+    require_gpu(g, a, w, chunks, chunk_ptr, mask_in_bits, mask_out_bits)
+    assert mlp_bwd_fused_supported(g, a, w) and nchunks > 0
+    N, H = g.shape
+    assert (mask_in_bits is None) == (mask_out_bits is None)
+    for m in (mask_in_bits, mask_out_bits):
+        assert m is None or (m.dtype == torch.uint8 and m.shape == (N, H // 8) and m.is_contiguous())
+    gw = torch.empty((H, H), dtype=w.dtype, device=g.device)
+    colsum = torch.empty((H,), dtype=torch.float32, device=g.device)
+    gb = torch.empty((H,), dtype=w.dtype, device=g.device)
+    g_next = torch.empty_like(g)
+    ws = _ws(lib().dn_rows_wgrad_workspace_bytes(nchunks, H, H), g.device)
+
+    def _launch():
+        check(lib().dn_mlp_bwd_fused_bf16(ptr(g), ptr(a), ptr(w), ptr(mask_in_bits), ptr(mask_out_bits), N, H, ptr(chunks), nchunks,
+                                          ptr(chunk_ptr), ptr(gw), 0, ptr(colsum), ptr(gb), ptr(g_next), float(slope), ptr(ws),
+                                          ws.numel(), stream_ptr()), "dn_mlp_bwd_fused_bf16")
+    if kernel_timer is not None:
+        kernel_timer.launch("mlp_bwd_fused", _launch)
+    else:
+        _launch()
+    return gw, gb, g_next
+
+
 class _ReluMlpFn(torch.autograd.Function):
     """y_L = act(lin_L(... act(lin_1(x)))) with every Linear followed by the activation -- ReLU (slope 0) or leaky ReLU (the
     reference MLP + final activation, rgin.py:50-57,147-151, for act_func "relu" and for its CLI default "leaky_relu", slope
     1 / 5.5: config.py:329-335, utils/act.py:466).
     Two layers in bf16 (the reference default): ONE forward launch (dn_rows_chain2_bf16) that also emits both activation masks
-    as bit tensors (sign of the output = sign of the pre-activation for either activation), and three backward launches: weight
-    gradient of layer 2 (outer mask applied from its bits while the rows are staged), the whole input-gradient chain (mask,
-    dgrad 2, mask, dgrad 1), weight gradient of layer 1.
+    as bit tensors (sign of the output = sign of the pre-activation for either activation).  Backward at H = 256 from
+    MLP_BWD_FUSED_MIN_ROWS rows on: TWO launches
+    (dn_mlp_bwd_fused_bf16 per layer: outer mask, weight + bias gradient and the masked input gradient in one pass over the layer's
+    rows; the weight gradient alone for layer 1 when the input needs no gradient), each followed by its reduce.  Other widths, smaller batches and
+    DN_MLP_BWD_FUSED=0: three launches -- weight gradient of layer 2 (outer mask applied from its bits while the rows are staged),
+    the whole input-gradient chain (mask, dgrad 2, mask, dgrad 1), weight gradient of layer 1 -- with bit-identical results.
     Otherwise: one fused Linear+bias+activation launch per layer forward; per layer backward a weight/bias-gradient launch and
     an input-gradient launch whose epilogue applies the activation mask of the layer below."""
 
@@ -2331,6 +2378,21 @@ class _ReluMlpFn(torch.autograd.Function):
         if ctx.chain:
             x0, h1, bits1, bits2, w1, w2 = saved
             _, chunks = _dense_table(x0.shape[0], x0.device)
+            if (MLP_BWD_FUSED_ENABLED and x0.shape[0] >= MLP_BWD_FUSED_MIN_ROWS and mlp_bwd_fused_supported(g, h1, w2)
+                    and mlp_bwd_fused_supported(g, x0, w1)):
+                gw2, gb2, g1 = mlp_bwd_fused(g, h1, w2, chunks, mask_in_bits=bits2, mask_out_bits=bits1, slope=slope)
+                if ctx.needs_input_grad[0]:
+                    gw1, gb1, g0 = mlp_bwd_fused(g1, x0, w1, chunks, slope=slope)
+                else:
+                    gw1, cs1 = rows_wgrad(g1, x0, chunks, 1, out_dtype=w1.dtype, colsum_of=1, colsum_lp=True)
+                    gw1, gb1, g0 = gw1[0], cs1[0], None
+                grads[2], grads[4] = gw1, gw2
+                if ctx.has_bias[0]:
+                    grads[3] = gb1.to(g.dtype)
+                if ctx.has_bias[1]:
+                    grads[5] = gb2.to(g.dtype)
+                grads[0] = g0
+                return tuple(grads)
             gw2, cs2 = rows_wgrad(g, h1, chunks, 1, out_dtype=w2.dtype, colsum_of=1, mask_a_bits=bits2, colsum_lp=True, slope=slope)
             g1, g0 = rows_chain2(g, w2, None, False, w1, None, False, mask0_bits=bits2, mask1_bits=bits1, w_kn=(True, True),
                                  slope=slope)

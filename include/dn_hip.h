@@ -675,6 +675,23 @@ int dn_rows_chain2_bf16(const void* X, int32_t H, const void* W1n, const void* b
                         const void* mask1_bits, const void* W2n, const void* b2, int32_t relu2, int64_t N, void* Y1, void* Y2,
                         void* bits1, void* bits2, int32_t w_kn, float act_slope, dn_stream_t stream);
 
+/* One Linear's whole backward in ONE pass over its rows (bf16, H = 256): weight gradient, bias gradient and input gradient.
+ *   Gm     = mask_in_bits ? keep_or_scale(G, mask_in_bits) : G
+ *   out_w  = sum_p Gm[p, :]^T A[p, :]   ([H, H], fp32 or bf16: out_is_f32)      out_colsum = colsum(Gm)  (fp32 [H])
+ *   g_next = mask_out_bits ? keep_or_scale(Gm @ W_kn, mask_out_bits) : Gm @ W_kn          (bf16 [N, H])
+ * G: the gradient of the Linear's (activated) output, A: the Linear's input rows, W_kn: nn.Linear.weight as the parameter
+ * stores it ([out = k][in = n]).  mask_in_bits / mask_out_bits (both or neither): the bit tensors of dn_rows_chain2_bf16 (uint8
+ * [N, H/8]) -- the activation behind this Linear and the one in front of it; act_slope as everywhere (0 = ReLU).
+ * chunks / chunk_ptr: a split-K row-chunk table of ONE relation over rows [0, N) as dn_rows_wgrad_bf16 takes it; workspace:
+ * dn_rows_wgrad_workspace_bytes(num_chunks, H, H).  out_colsum_lp (may be NULL): the column sums again in out_w's element type.
+ * The reference MLP's backward (subgraph_isomorphism/models/rgin.py:50-57 + the layer activation) is this call twice -- layer 2
+ * with both masks, layer 1 on its g_next without -- and every result is bit-identical to dn_rows_wgrad_bf16 (mask_a_bits) +
+ * dn_rows_chain2_bf16 (w_kn = 3, both masks) + dn_rows_wgrad_bf16 on the same chunk table: same tiles, same order, same rounding. */
+int dn_mlp_bwd_fused_bf16(const void* G, const void* A, const void* W_kn, const void* mask_in_bits, const void* mask_out_bits,
+                          int64_t N, int32_t H, const int32_t* chunks, int64_t num_chunks, const int32_t* chunk_ptr, void* out_w,
+                          int32_t out_is_f32, float* out_colsum, void* out_colsum_lp, void* g_next, float act_slope,
+                          void* workspace, size_t workspace_bytes, dn_stream_t stream);
+
 /* ReLU backward of the post-aggregate MLP (act_func "relu": utils/act.py:463; applied at rgin.py:56,147-151):
  * out = (y > 0) ? g : 0 on bf16 tensors of `numel` elements (multiple of 8).  The same mask is available as the
  * `mask_pos` epilogue of dn_rows_transform_bf16 ([rows, Ho] saved activations), so a Linear's input gradient comes
