@@ -107,7 +107,7 @@ __global__ void edge_norm_kernel(int32_t mode, int64_t E, const int32_t* __restr
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (e >= E) return;
     if (mode == 1) edge_norm[e] = in_norm[dst[e]];
-    else edge_norm[e] = __fsqrt_rn(out_norm[src[e]] * in_norm[dst[e]]);
+    else edge_norm[e] = sqrtf(out_norm[src[e]] * in_norm[dst[e]]);      // correctly rounded (__fsqrt_rn is the native approximation here)
 }
 
 // ----- dummy augmentation -------------------------------------------------------------------------
