@@ -6,6 +6,7 @@ current stream and autograd bookkeeping.  There is deliberately no CPU path.
 import ctypes
 import os as _os
 import threading as _threading
+from typing import NamedTuple
 
 import torch
 
@@ -47,6 +48,14 @@ class KernelTimer:
 
 
 kernel_timer = None  # set to a KernelTimer by bench.py
+
+
+def launch_tagged(tag, fn):
+    """fn() under kernel_timer's tag when a timer is set (read at call time: bench.py and the tests assign the module global).
+    The benchmark counts launches by tag, so every kernel launch of a step goes through here; the table builders stay untagged."""
+    if kernel_timer is not None:
+        return kernel_timer.launch(tag, fn)
+    return fn()
 
 
 def _suffix(t):
@@ -101,10 +110,7 @@ def gather_segsum(x, idx=None, ptr_=None, num_segments=None, scale=None, self_in
         check(fn(ptr(x), x.shape[0], H, ptr(idx), ptr(scale), ptr(ptr_), S, M, ptr(out), ptr(self_in),
                  float(self_coef), 1 if mean else 0, stream_ptr()), "dn_gather_segsum")
 
-    if kernel_timer is not None:
-        kernel_timer.launch("gather_segsum", _launch)
-    else:
-        _launch()
+    launch_tagged("gather_segsum", _launch)
     return out
 
 
@@ -149,10 +155,7 @@ def gather_rows_sum(x, idx, ptr_, rows, workgroup_per_row, self_coef, out):
         check(lib().dn_gather_rows_sum_f32(ptr(x), int(x.shape[1]), ptr(ptr_), ptr(idx), ptr(rows), 1 if records else 0,
                                            int(rows.shape[0]), 1 if workgroup_per_row else 0, float(self_coef), ptr(out),
                                            stream_ptr()), "dn_gather_rows_sum_f32")
-    if kernel_timer is not None:
-        kernel_timer.launch("gather_rows_sum", _launch)
-    else:
-        _launch()
+    launch_tagged("gather_rows_sum", _launch)
     return out
 
 
@@ -176,10 +179,7 @@ def graph_tile_sum(x, idx, ptr_, tiles, self_coef=0.0, out=None, seg=None, bad=N
                                           ptr(seg) if seg is not None else None, int(idx.numel()), ptr(tiles),
                                           int(tiles.shape[0]), float(self_coef), ptr(out), ptr(bad), stream_ptr()),
               "dn_graph_tile_sum_f32")
-    if kernel_timer is not None:
-        kernel_timer.launch("graph_tile_sum", _launch)
-    else:
-        _launch()
+    launch_tagged("graph_tile_sum", _launch)
     return out, bad
 
 
@@ -325,10 +325,7 @@ def rows_wgrad(A, G, chunk_table, num_rels, idx_a=None, idx_g=None, out_dtype=No
                                            ptr(a_out), ptr(mask_a_bits), ptr(colsum_lp), float(slope), ptr(ws), ws.numel(), stream_ptr()),
                   "dn_rows_wgrad_bf16")
 
-    if kernel_timer is not None:
-        kernel_timer.launch("rows_wgrad", _launch)
-    else:
-        _launch()
+    launch_tagged("rows_wgrad", _launch)
     if colsum_of:
         return out, (colsum_lp if colsum_lp is not None else colsum)
     return out
@@ -374,10 +371,7 @@ def rows_wgrad_multi(jobs, chunk_table, num_rels, H, out_dtype):
         check(lib().dn_rows_wgrad_multi_bf16(arr, len(jobs), H, num_rels, ptr(chunks), nchunks, ptr(chunk_ptr), ptr(out),
                                              1 if out_dtype == torch.float32 else 0, ptr(colsum), ptr(colsum_lp), ptr(ws), ws.numel(),
                                              stream_ptr()), "dn_rows_wgrad_multi_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("rows_wgrad_multi", _launch)
-    else:
-        _launch()
+    launch_tagged("rows_wgrad_multi", _launch)
     return out, (colsum_lp if colsum_lp is not None else colsum)
 
 
@@ -490,10 +484,7 @@ def rows_transform(X, Wn, tile_table, num_rows, idx=None, X2=None, bias=None, re
                                                ptr(mask_pos), ptr(tiles), ntiles, ptr(Y), 1 if w_kn else 0, float(slope), stream_ptr()),
                   "dn_rows_transform_bf16")
 
-    if kernel_timer is not None:
-        kernel_timer.launch("rows_transform:" + tag, _launch)
-    else:
-        _launch()
+    launch_tagged("rows_transform:" + tag, _launch)
     return Y
 
 
@@ -545,10 +536,7 @@ def rows_selfsum(x, Wn, bias, S, S2, slots, out=None, seg=None, lists=None, w_kn
                                          ptr(seg[0]) if seg else None, ptr(seg[1]) if seg else None, 1 if w_kn else 0,
                                          ptr(lin[0]), ptr(lin[1]), int(lin[2]), int(lin[3]), int(lin[4]), stream_ptr()),
               "dn_rows_selfsum_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("rows_selfsum", _launch)
-    else:
-        _launch()
+    launch_tagged("rows_selfsum", _launch)
     if lists is not None and not inside:
         lp, lr, ner, db, de, over = lists[:6]
         require_gpu(lp, lr, over)
@@ -559,10 +547,7 @@ def rows_selfsum(x, Wn, bias, S, S2, slots, out=None, seg=None, lists=None, w_kn
             check(lib().dn_overflow_rows_add_bf16(ptr(S) if S is not None and S.numel() else None, H, ptr(over), SELFSUM_SLOTS, N,
                                                   ptr(lp), ptr(lr), int(ner), int(db), int(de), ptr(out), stream_ptr()),
                   "dn_overflow_rows_add_bf16")
-        if kernel_timer is not None:
-            kernel_timer.launch("overflow_rows_add", _launch2)
-        else:
-            _launch2()
+        launch_tagged("overflow_rows_add", _launch2)
     return out
 
 
@@ -590,10 +575,7 @@ def rows_chain2(x, W1n, b1, relu1, W2n, b2, relu2, mask0_bits=None, mask1_bits=N
                                         ptr(W2n), ptr(b2), 1 if relu2 else 0, N, ptr(Y1), ptr(Y2), ptr(bits1), ptr(bits2),
                                         (1 if w_kn[0] else 0) | (2 if w_kn[1] else 0), float(slope), stream_ptr()),
               "dn_rows_chain2_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("rows_chain2", _launch)
-    else:
-        _launch()
+    launch_tagged("rows_chain2", _launch)
     return (Y1, Y2, bits1, bits2) if want_bits else (Y1, Y2)
 
 
@@ -615,10 +597,7 @@ def rows_chain2_f32(x, W1n, b1, relu1, W2n, b2, relu2, mask0=None, mask1=None, w
         check(lib().dn_rows_chain2_f32(ptr(x), H, ptr(W1n), ptr(b1), 1 if relu1 else 0, ptr(mask0), ptr(mask1), ptr(W2n), ptr(b2),
                                        1 if relu2 else 0, N, ptr(Y1), ptr(Y2), (1 if w_kn[0] else 0) | (2 if w_kn[1] else 0), float(slope),
                                        ptr(residual), ptr(Ysum), stream_ptr()), "dn_rows_chain2_f32")
-    if kernel_timer is not None:
-        kernel_timer.launch("rows_chain2", _launch)
-    else:
-        _launch()
+    launch_tagged("rows_chain2", _launch)
     return (Y1, Y2, Ysum) if residual is not None else (Y1, Y2)
 
 
@@ -794,10 +773,7 @@ def rows_close(x, W, bias, S, cu, out=None, seg=None, w_kn=False, agg=None):
         check(lib().dn_rows_close_bf16(ptr(x), H, ptr(W), 1 if w_kn else 0, ptr(bias), ptr(S) if S is not None and S.numel() else None,
                                        ptr(cu.unit_ptr), ptr(cu.units), cu.num_wg, ptr(cu.ent_row), ptr(cu.ent_mask), N, ptr(out),
                                        ptr(fi), ptr(sp), ptr(wa), ptr(ax), ptr(ai), stream_ptr()), "dn_rows_close_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("rows_close", _launch)
-    else:
-        _launch()
+    launch_tagged("rows_close", _launch)
     return out
 
 
@@ -1193,10 +1169,7 @@ def rows_gemm(A, W, tile_table, transpose_w=False, bias=None):
     def _launch():
         check(getattr(lib(), "dn_rows_gemm_" + _suffix(A))(ptr(A), ptr(W), ptr(bias), K, N, 1 if transpose_w else 0, ptr(tiles),
                                                           ntiles, ptr(Y), stream_ptr()), "dn_rows_gemm")
-    if kernel_timer is not None:
-        kernel_timer.launch("rows_gemm", _launch)
-    else:
-        _launch()
+    launch_tagged("rows_gemm", _launch)
     return Y
 
 
@@ -1337,6 +1310,59 @@ LOCAL_INDEX_ENABLED = _os.environ.get("DN_LOCAL_INDEX", "1") != "0"
 CONV_INDEX_ENABLED = _os.environ.get("DN_CONV_INDEX", "1") != "0"
 
 
+class RowDirection(NamedTuple):
+    """The tables ONE direction of a pass over a RowIndex reads ('f': the forward pass, 'b': its mirror image)."""
+    aux_ptr: torch.Tensor        # pre-aggregation lists of the collapsed relations (AGG forward / TF backward): [n_aux + 1]
+    aux_idx: torch.Tensor        # ... their entries
+    n_aux: int
+    rows_in: torch.Tensor        # the row every row of the set gathers (row_in forward, row_out backward)
+    rows_out: torch.Tensor       # ... and the row its product is added to
+    list_ptr: torch.Tensor       # per node, the rows added to it: [N + 1]
+    list_rows: torch.Tensor
+
+
+class _Absorbed(NamedTuple):
+    """What the graph-local builders report per direction on the ABSORBED fold (a graph = a segment of the collapsed relation)."""
+    tile_ptr: torch.Tensor       # [G + 1] graph tiles
+    fold_info: torch.Tensor      # [G, 12]
+    verdict: int                 # bit 0: every block within 32 nodes; bit 1: valid without that limit
+
+
+class _ConvPlan(NamedTuple):
+    """What dn_conv_index_build_i32 left behind beside the row index (RowIndex._adopt_plan hands it on to _fold / _units)."""
+    units: list                  # CloseUnits of 'f' / 'b': the unit streams of both closing launches
+    sweeps: list                 # per direction the sweep order (tiles, #tiles), or None
+    chunk_table: tuple           # (chunks, chunk_ptr, #chunks) of the weight gradient
+    served: tuple                # per direction 0: not served, 1: every graph within one tile, 2: the chunked (multi-tile) form
+    multi_views: object          # k -> (chunk_tile, chunk_graph, tile_ptr, fold_info) of direction k's chunked form
+    multi_tiles: int             # ... and its tile count
+
+
+class _IndexBuffers:
+    """Output tables of the row-index builders, allocated ONCE: whichever builder serves the batch fills the same buffers.  G (a batch
+    with graph boundaries): also what the graph-local builders write on top -- their status, the relation offsets as they leave them
+    on the device, the absorbed-fold verdicts + graph tiles of both directions (same call, same read-back)."""
+
+    def __init__(self, N, R, E, dev, G=None):
+        self.e32 = e32 = lambda n: torch.empty(max(int(n), 1), dtype=I32, device=dev)  # noqa: E731
+        self.row_in, self.row_out = e32(E + N), e32(E + N)
+        self.aux_f_ptr, self.aux_f_idx, self.aux_b_ptr, self.aux_b_idx = e32(E + 1), e32(E), e32(E + 1), e32(E)
+        self.dst_ptr, self.dst_rows, self.src_ptr, self.src_rows = e32(N + 2), e32(2 * E + N), e32(N + 2), e32(2 * E + N)
+        self.counts = (ctypes.c_int64 * 5)()
+        self.host_rel = (ctypes.c_int32 * (R + 1))()
+        self.host_modes = (ctypes.c_int32 * R)()
+        if G is not None:
+            self.rel_dev = e32(R + 2)
+            self.graph_tiles = [(e32(G + 1), torch.empty((max(G, 1), 12), dtype=I32, device=dev)) for _ in range(2)]
+            self.host_absorb = (ctypes.c_int32 * 4)()              # fold verdicts f / b, the largest graph's nodes / edges
+            self.status, gt = ctypes.c_int32(0), self.graph_tiles
+            self.local_args = (ctypes.byref(self.status), ptr(self.rel_dev), ptr(gt[0][0]), ptr(gt[0][1]), ptr(gt[1][0]), ptr(gt[1][1]),
+                               self.host_absorb)
+        # the tables in the order every builder takes them
+        self.args = (ptr(self.row_in), ptr(self.row_out), ptr(self.aux_f_ptr), ptr(self.aux_f_idx), ptr(self.aux_b_ptr), ptr(self.aux_b_idx),
+                     ptr(self.dst_ptr), ptr(self.dst_rows), ptr(self.src_ptr), ptr(self.src_rows), self.counts, self.host_rel, self.host_modes)
+
+
 class RowIndex:
     """Relation-major ROW FACTORISATION of  out[v] = sum_{e: dst(e)=v} x[src(e)] W[etype(e)]  (+ x[v] W_loop).
 
@@ -1353,186 +1379,229 @@ class RowIndex:
 
     def __init__(self, src, dst, etype, num_nodes, num_rels, self_loop=True, edge_frac=0.75, node_ptr=None, edge_ptr=None,
                  closing_hint=None):
-        """One C-ABI call + device-side tile tables.  With the batch's graph boundaries (node_ptr / edge_ptr, [G+1] each) the
-        graph-local builder runs (dn_row_index_build_local_i32: one wavefront rank-sorts one graph in LDS, one scan); without
-        them, or when the batch does not qualify (a graph of 8192 edges or more, more than 64 relations), the general one
-        (dn_row_index_build_i32: stable radix sorts + scans over the whole batch).  Both produce the same tables bit for bit.
-        closing_hint = (H, dtype) of the rows the index will serve: for (256, bfloat16) with graph boundaries the WHOLE per-batch
-        index -- row index, unit streams of both closing launches, sweep orders, weight-gradient chunk table -- is one call with one
-        read-back (dn_conv_index_build_i32); whatever that call could not serve is built on first use as before."""
+        """One C-ABI call + device-side tile tables.  With the batch's graph boundaries (node_ptr / edge_ptr, [G+1] each) a
+        graph-local builder runs -- _build_one_call where closing_hint, the (H, dtype) of the rows the index will serve, is
+        (256, bfloat16), else _build_local; without them, or when the batch does not qualify (a graph of 8192 edges or more, more
+        than 64 relations), the general one (_build_general).  All produce the same tables bit for bit."""
         require_gpu(src, dst, etype)
-        dev = src.device
         N, R, E = int(num_nodes), int(num_rels), int(src.numel())
         self.num_nodes, self.num_rels, self.num_edges, self.self_loop = N, R, E, bool(self_loop)
-        try_local = node_ptr is not None and edge_ptr is not None and R <= 64 and LOCAL_INDEX_ENABLED
-        if try_local:                                                 # (graphs over the LDS limit: do not even try)
-            try_local = E == 0 or E < 8192 * (int(node_ptr.numel()) - 1)
-        if not try_local:
-            _check_edge_types(etype, R)                               # (the local builder validates on the device)
-        src, dst, etype = (t.to(I32).contiguous() for t in (src, dst, etype))
-        e32 = lambda n: torch.empty(max(int(n), 1), dtype=I32, device=dev)  # noqa: E731
-        row_in, row_out = e32(E + N), e32(E + N)
-        aux_f_ptr, aux_f_idx, aux_b_ptr, aux_b_idx = e32(E + 1), e32(E), e32(E + 1), e32(E)
-        dst_ptr, dst_rows, src_ptr, src_rows = e32(N + 2), e32(2 * E + N), e32(N + 2), e32(2 * E + N)
-        counts = (ctypes.c_int64 * 5)()
-        host_rel = (ctypes.c_int32 * (R + 1))()
-        host_modes = (ctypes.c_int32 * R)()
-        self.built_by = "general"
-        self.max_graph = None                                         # local builder: (nodes, edges) of the batch's largest graph
+        self.built_by = "general"                                     # which builder served the batch: "local" (either graph-local call) / "general"
+        self.max_graph = None                                         # local builders: (nodes, edges) of the batch's largest graph
         self.raw = None                                               # ... and (src, dst, etype, node_ptr, edge_ptr) int32
-        self._absorb = None                                           # local builder: {direction: (tile_ptr, fold_info, verdict)}
-        rel_dev = None
-        pre = None                                                    # (tables dn_conv_index_build_i32 left behind, see below)
+        self._absorb = None                                           # ... and {direction: _Absorbed}
+        self._cg_err = None                                           # error / statistics words of the whole-graph launches (_graphs_err)
+        self._layer_chunks = {}                                       # virtual-row chunk tables of the layer functions, by cut (layer_wgrad)
+        try_local = node_ptr is not None and edge_ptr is not None and R <= 64 and LOCAL_INDEX_ENABLED
+        G = int(node_ptr.numel()) - 1 if try_local else None
+        if try_local:                                                 # (graphs over the LDS limit: do not even try)
+            try_local = E == 0 or E < 8192 * G
+        if not try_local:
+            _check_edge_types(etype, R)                               # (the local builders validate on the device)
+        src, dst, etype = (t.to(I32).contiguous() for t in (src, dst, etype))
+        bufs, plan = _IndexBuffers(N, R, E, src.device, G if try_local else None), None
         if try_local:
             require_gpu(node_ptr, edge_ptr)
-            rel_dev = e32(R + 2)                                      # the relation offsets as the device builder leaves them
-            node_ptr, edge_ptr = node_ptr.to(I32).contiguous(), edge_ptr.to(I32).contiguous()
-            G = int(node_ptr.numel()) - 1
-            # the absorbed-fold verdicts + graph tiles of both directions come out of the same call (and the same read-back)
-            gt_bufs = [(e32(G + 1), torch.empty((max(G, 1), 12), dtype=I32, device=dev)) for _ in range(2)]
-            host_absorb = (ctypes.c_int32 * 4)()                       # fold verdicts f / b, the largest graph's nodes / edges
-            assert G >= 0 and int(edge_ptr.numel()) == G + 1
-            one_call = (CONV_INDEX_ENABLED and CLOSE_SINGLE_ENABLED and closing_hint is not None and closing_hint[0] == 256
-                        and closing_hint[1] == torch.bfloat16 and self_loop and G >= 1 and N >= 1 and CLOSE_RING_ENABLED
-                        and CLOSE_AGG_ENABLED and FOLD_ENABLED)
-            nbytes = 0 if one_call else lib().dn_row_index_local_workspace_bytes(G, N, R, E)
-            if one_call:
-                num_wg = _num_cus(dev)
-                # (a graph over 32 nodes: the same call builds the chunked tiles and their unit streams instead; which, is decided on the device)
-                kper = close_chunks(N, num_wg) // num_wg if CLOSE_MULTI_ENABLED else 0
-                tcap = int(lib().dn_fold_graph_tiles_multi_capacity(N, kper * num_wg)) if kper else 0
-                nbytes = lib().dn_conv_index_workspace_bytes(G, N, R, E, num_wg, tcap)
-            if one_call and nbytes:
-                cap = int(lib().dn_close_units_capacity(max(G, tcap), E + N, num_wg))
-                # the chunked form's eight tables out of ONE allocation (most batches never look at them: views are made on demand)
-                mt_sizes = (kper * num_wg + 1, kper * num_wg + 1, tcap + 1, 12 * max(tcap, 1))
-                mt_off, acc = [], 0
-                for _ in range(2):
-                    for n_ in mt_sizes:
-                        mt_off.append(acc)
-                        acc += (n_ + 3) // 4 * 4                        # (16-byte aligned pieces)
-                mt_arena = e32(acc) if kper else None
-                mt_ptr = [ctypes.c_void_p(mt_arena.data_ptr() + 4 * o) if kper else None for o in mt_off]
-
-                def mt_views(k):
-                    o = mt_off[4 * k:4 * k + 4]
-                    return (mt_arena[o[0]:o[0] + mt_sizes[0]], mt_arena[o[1]:o[1] + mt_sizes[1]], mt_arena[o[2]:o[2] + mt_sizes[2]],
-                            mt_arena[o[3]:o[3] + mt_sizes[3]].view(max(tcap, 1), 12))
-                cus = []
-                for _ in range(2):
-                    cu = CloseUnits()
-                    cu.num_wg, cu.num_nodes, cu.agg, cu.num_tiles, cu.order, cu.num_segments = num_wg, N, True, G, _close_order(num_wg), G
-                    cu.unit_ptr, cu.units = e32(num_wg + 1), torch.empty((cap, 4), dtype=I32, device=dev)
-                    cu.ent_row, cu.ent_mask = e32(E + N), e32(E + N)
-                    cus.append(cu)
-                Gw = 8 * SWEEP_WG_PER_GROUP
-                want_sweep = SWEEP_ENABLED and E // 32 >= Gw * SWEEP_MIN_TILES_PER_WG
-                S = int(1.10 * (E // 32 + 8 * R) / Gw) + 4 if want_sweep else 0
-                sweeps = [torch.empty((Gw * S, 4), dtype=I32, device=dev) for _ in range(2)] if want_sweep else [None, None]
-                chunk_cap = (E + N) // 256 + R + 3
-                chunk_tab, chunk_pp = torch.empty((chunk_cap, 4), dtype=I32, device=dev), e32(R + 2)
-                host_plan = (ctypes.c_int32 * 6)()
-                ws = _ws(nbytes, dev)
-                status = ctypes.c_int32(0)
-                check(lib().dn_conv_index_build_i32(
-                    G, N, R, E, ptr(node_ptr), ptr(edge_ptr), ptr(src), ptr(dst), ptr(etype), 1, float(edge_frac), ptr(row_in),
-                    ptr(row_out), ptr(aux_f_ptr), ptr(aux_f_idx), ptr(aux_b_ptr), ptr(aux_b_idx), ptr(dst_ptr), ptr(dst_rows),
-                    ptr(src_ptr), ptr(src_rows), counts, host_rel, host_modes, ctypes.byref(status), ptr(rel_dev), ptr(gt_bufs[0][0]),
-                    ptr(gt_bufs[0][1]), ptr(gt_bufs[1][0]), ptr(gt_bufs[1][1]), host_absorb, num_wg, cus[0].order, cap, ptr(cus[0].unit_ptr),
-                    ptr(cus[0].units), ptr(cus[0].ent_row), ptr(cus[0].ent_mask), ptr(cus[1].unit_ptr), ptr(cus[1].units),
-                    ptr(cus[1].ent_row), ptr(cus[1].ent_mask), kper, tcap, *mt_ptr, SWEEP_WG_PER_GROUP, S, ptr(sweeps[0]), ptr(sweeps[1]), 256,
-                    WGRAD_CHUNK_CAP, chunk_cap, ptr(chunk_tab), ptr(chunk_pp), host_plan, ptr(ws), ws.numel(), stream_ptr()),
-                    "dn_conv_index_build_i32")
-                if status.value == 0:
-                    self.built_by = "local"
-                    self._absorb = {d: (gt_bufs[k][0], gt_bufs[k][1], int(host_absorb[k])) for k, d in enumerate(("f", "b"))}
-                    self.max_graph = (int(host_absorb[2]), int(host_absorb[3]))
-                    # (the sweep tables were sized by a bound; the builder laid them out with the slots they need)
-                    sw = [(sweeps[k][:Gw * host_plan[4 + k]], Gw * int(host_plan[4 + k])) if want_sweep and host_plan[4 + k] > 0 else None
-                          for k in range(2)]
-                    pre = (cus, sw, (chunk_tab, chunk_pp, int(host_plan[3])), int(host_plan[0]), int(host_plan[1]), mt_views, tcap)
-            elif nbytes:
-                ws = _ws(nbytes, dev)
-                status = ctypes.c_int32(0)
-                check(lib().dn_row_index_build_local_i32(G, N, R, E, ptr(node_ptr), ptr(edge_ptr), ptr(src), ptr(dst), ptr(etype),
-                                                         1 if self_loop else 0, float(edge_frac), ptr(row_in), ptr(row_out),
-                                                         ptr(aux_f_ptr), ptr(aux_f_idx), ptr(aux_b_ptr), ptr(aux_b_idx),
-                                                         ptr(dst_ptr), ptr(dst_rows), ptr(src_ptr), ptr(src_rows), counts, host_rel,
-                                                         host_modes, ctypes.byref(status), ptr(rel_dev), ptr(gt_bufs[0][0]),
-                                                         ptr(gt_bufs[0][1]), ptr(gt_bufs[1][0]), ptr(gt_bufs[1][1]), host_absorb,
-                                                         ptr(ws), ws.numel(), stream_ptr()),
-                      "dn_row_index_build_local_i32")
-                if status.value == 0:
-                    self.built_by = "local"
-                    self._absorb = {d: (gt_bufs[k][0], gt_bufs[k][1], int(host_absorb[k])) for k, d in enumerate(("f", "b"))}
-                    self.max_graph = (int(host_absorb[2]), int(host_absorb[3]))
-            if self.built_by == "local":                              # the batch itself, for the launches that take graphs whole
-                self.raw = (src, dst, etype, node_ptr, edge_ptr)
-            if self.built_by != "local":
+            batch = (src, dst, etype, node_ptr.to(I32).contiguous(), edge_ptr.to(I32).contiguous())
+            assert G >= 0 and int(batch[4].numel()) == G + 1
+            if self._one_call_wanted(closing_hint, G):                # (a batch this call turns down goes to the general builder)
+                plan = self._build_one_call(bufs, batch, edge_frac)
+                served = plan is not None
+            else:
+                served = self._build_local(bufs, batch, edge_frac)
+            if not served:
                 _check_edge_types(etype, R)
         if self.built_by == "general":
-            nbytes = lib().dn_row_index_workspace_bytes(N, R, E)
-            if nbytes == 0:
-                check(-2, "dn_row_index_workspace_bytes")
-            ws = _ws(nbytes, dev)
-            check(lib().dn_row_index_build_i32(N, R, E, ptr(src), ptr(dst), ptr(etype), 1 if self_loop else 0, float(edge_frac),
-                                               ptr(row_in), ptr(row_out), ptr(aux_f_ptr), ptr(aux_f_idx), ptr(aux_b_ptr),
-                                               ptr(aux_b_idx), ptr(dst_ptr), ptr(dst_rows), ptr(src_ptr), ptr(src_rows), counts,
-                                               host_rel, host_modes, ptr(ws), ws.numel(), stream_ptr()), "dn_row_index_build_i32")
-        P, n_agg, n_tf, n_agg_e, n_tf_e = (int(v) for v in counts)
-        self.modes = [int(m) for m in host_modes]
-        rel_ptr = [int(v) for v in host_rel]
+            self._build_general(bufs, src, dst, etype, edge_frac)
+        self._publish(bufs)
+        # one workgroup per CU (the LDS-DMA ring fills a CU's LDS) for the split-K weight gradient whatever the batch size:
+        # the smallest chunk that keeps ALL relations' chunks (each relation ends in a partial one) within one round of 256
+        if plan is not None:
+            self._adopt_plan(plan)
+        else:
+            self.chunk_table = build_row_tables(self.rel_ptr_dev, self.num_all_rels, self.num_rows, wgrad_chunk_rows(self.rel_ptr_host),
+                                                want_ptr=True)
+
+    def _one_call_wanted(self, closing_hint, G):
+        return (CONV_INDEX_ENABLED and CLOSE_SINGLE_ENABLED and closing_hint is not None and closing_hint[0] == 256
+                and closing_hint[1] == torch.bfloat16 and self.self_loop and G >= 1 and self.num_nodes >= 1 and CLOSE_RING_ENABLED
+                and CLOSE_AGG_ENABLED and FOLD_ENABLED)
+
+    def _served_by_local(self, bufs, batch):
+        """Did the graph-local builder that just ran serve the batch?  If so: what either leaves on the index beside the tables."""
+        if bufs.status.value != 0:
+            return False
+        self.built_by = "local"
+        self._absorb = {d: _Absorbed(bufs.graph_tiles[k][0], bufs.graph_tiles[k][1], int(bufs.host_absorb[k]))
+                        for k, d in enumerate(("f", "b"))}
+        self.max_graph = (int(bufs.host_absorb[2]), int(bufs.host_absorb[3]))
+        self.raw = batch                                              # the batch itself, for the launches that take graphs whole
+        return True
+
+    def _build_one_call(self, bufs, batch, edge_frac):
+        """dn_conv_index_build_i32: the WHOLE per-batch index of the H = 256 bf16 conv -- row index, unit streams of both closing
+        launches, sweep orders, weight-gradient chunk table -- in one call with one read-back; whatever it could not serve is built on
+        first use.  -> the _ConvPlan it left behind, or None where it did not serve the batch."""
+        src, dst, etype, node_ptr, edge_ptr = batch
+        N, R, E, dev, e32 = self.num_nodes, self.num_rels, self.num_edges, src.device, bufs.e32
+        G = int(node_ptr.numel()) - 1
+        num_wg = _num_cus(dev)
+        # (a graph over 32 nodes: the same call builds the chunked tiles and their unit streams instead; which, is decided on the device)
+        kper = close_chunks(N, num_wg) // num_wg if CLOSE_MULTI_ENABLED else 0
+        tcap = int(lib().dn_fold_graph_tiles_multi_capacity(N, kper * num_wg)) if kper else 0
+        nbytes = lib().dn_conv_index_workspace_bytes(G, N, R, E, num_wg, tcap)
+        if not nbytes:
+            return None
+        cap = int(lib().dn_close_units_capacity(max(G, tcap), E + N, num_wg))
+        # the chunked form's eight tables out of ONE allocation (most batches never look at them: views are made on demand)
+        mt_sizes = (kper * num_wg + 1, kper * num_wg + 1, tcap + 1, 12 * max(tcap, 1))
+        mt_off, acc = [], 0
+        for _ in range(2):
+            for n_ in mt_sizes:
+                mt_off.append(acc)
+                acc += (n_ + 3) // 4 * 4                                # (16-byte aligned pieces)
+        mt_arena = e32(acc) if kper else None
+        mt_ptr = [ctypes.c_void_p(mt_arena.data_ptr() + 4 * o) if kper else None for o in mt_off]
+
+        def mt_views(k):
+            o = mt_off[4 * k:4 * k + 4]
+            return (mt_arena[o[0]:o[0] + mt_sizes[0]], mt_arena[o[1]:o[1] + mt_sizes[1]], mt_arena[o[2]:o[2] + mt_sizes[2]],
+                    mt_arena[o[3]:o[3] + mt_sizes[3]].view(max(tcap, 1), 12))
+        cus = []
+        for _ in range(2):
+            cu = CloseUnits()
+            cu.num_wg, cu.num_nodes, cu.agg, cu.num_tiles, cu.order, cu.num_segments = num_wg, N, True, G, _close_order(num_wg), G
+            cu.unit_ptr, cu.units = e32(num_wg + 1), torch.empty((cap, 4), dtype=I32, device=dev)
+            cu.ent_row, cu.ent_mask = e32(E + N), e32(E + N)
+            cus.append(cu)
+        Gw = 8 * SWEEP_WG_PER_GROUP
+        want_sweep = SWEEP_ENABLED and E // 32 >= Gw * SWEEP_MIN_TILES_PER_WG
+        S = int(1.10 * (E // 32 + 8 * R) / Gw) + 4 if want_sweep else 0
+        sweeps = [torch.empty((Gw * S, 4), dtype=I32, device=dev) for _ in range(2)] if want_sweep else [None, None]
+        chunk_cap = (E + N) // 256 + R + 3
+        chunk_tab, chunk_pp = torch.empty((chunk_cap, 4), dtype=I32, device=dev), e32(R + 2)
+        host_plan = (ctypes.c_int32 * 6)()                             # [0], [1]: served f / b; [3]: #chunks; [4], [5]: sweep slots f / b
+        ws = _ws(nbytes, dev)
+        check(lib().dn_conv_index_build_i32(
+            G, N, R, E, ptr(node_ptr), ptr(edge_ptr), ptr(src), ptr(dst), ptr(etype), 1, float(edge_frac), *bufs.args,
+            *bufs.local_args, num_wg, cus[0].order, cap, ptr(cus[0].unit_ptr),
+            ptr(cus[0].units), ptr(cus[0].ent_row), ptr(cus[0].ent_mask), ptr(cus[1].unit_ptr), ptr(cus[1].units),
+            ptr(cus[1].ent_row), ptr(cus[1].ent_mask), kper, tcap, *mt_ptr, SWEEP_WG_PER_GROUP, S, ptr(sweeps[0]), ptr(sweeps[1]), 256,
+            WGRAD_CHUNK_CAP, chunk_cap, ptr(chunk_tab), ptr(chunk_pp), host_plan, ptr(ws), ws.numel(), stream_ptr()),
+            "dn_conv_index_build_i32")
+        if not self._served_by_local(bufs, batch):
+            return None
+        # (the sweep tables were sized by a bound; the builder laid them out with the slots they need)
+        sw = [(sweeps[k][:Gw * host_plan[4 + k]], Gw * int(host_plan[4 + k])) if want_sweep and host_plan[4 + k] > 0 else None
+              for k in range(2)]
+        return _ConvPlan(units=cus, sweeps=sw, chunk_table=(chunk_tab, chunk_pp, int(host_plan[3])),
+                         served=(int(host_plan[0]), int(host_plan[1])), multi_views=mt_views, multi_tiles=tcap)
+
+    def _build_local(self, bufs, batch, edge_frac):
+        """dn_row_index_build_local_i32: one wavefront rank-sorts one graph in LDS, one scan.  -> did it serve the batch?"""
+        src, dst, etype, node_ptr, edge_ptr = batch
+        N, R, E = self.num_nodes, self.num_rels, self.num_edges
+        G = int(node_ptr.numel()) - 1
+        nbytes = lib().dn_row_index_local_workspace_bytes(G, N, R, E)
+        if not nbytes:
+            return False
+        ws = _ws(nbytes, src.device)
+        check(lib().dn_row_index_build_local_i32(G, N, R, E, ptr(node_ptr), ptr(edge_ptr), ptr(src), ptr(dst), ptr(etype),
+                                                 1 if self.self_loop else 0, float(edge_frac), *bufs.args, *bufs.local_args,
+                                                 ptr(ws), ws.numel(), stream_ptr()),
+              "dn_row_index_build_local_i32")
+        return self._served_by_local(bufs, batch)
+
+    def _build_general(self, bufs, src, dst, etype, edge_frac):
+        """dn_row_index_build_i32: stable radix sorts + scans over the whole batch; serves every batch (edge types checked on the host)."""
+        N, R, E = self.num_nodes, self.num_rels, self.num_edges
+        nbytes = lib().dn_row_index_workspace_bytes(N, R, E)
+        if nbytes == 0:
+            check(-2, "dn_row_index_workspace_bytes")
+        ws = _ws(nbytes, src.device)
+        check(lib().dn_row_index_build_i32(N, R, E, ptr(src), ptr(dst), ptr(etype), 1 if self.self_loop else 0, float(edge_frac),
+                                           *bufs.args, ptr(ws), ws.numel(), stream_ptr()), "dn_row_index_build_i32")
+
+    def _publish(self, bufs):
+        """The builder's tables, cut to the sizes it reported, as the index's attributes."""
+        N, R, E, self_loop = self.num_nodes, self.num_rels, self.num_edges, self.self_loop
+        P, n_agg, n_tf, n_agg_e, n_tf_e = (int(v) for v in bufs.counts)
+        self.modes = [int(m) for m in bufs.host_modes]
+        rel_ptr = [int(v) for v in bufs.host_rel]
         P_all = P + (N if self_loop else 0)
         if self_loop:
             rel_ptr.append(P_all)
         self.num_aux_f, self.num_aux_b = n_agg, n_tf
-        self.aux_f_ptr, self.aux_f_idx = aux_f_ptr[:n_agg + 1], aux_f_idx[:max(n_agg_e, 1)][:n_agg_e]
-        self.aux_b_ptr, self.aux_b_idx = aux_b_ptr[:n_tf + 1], aux_b_idx[:max(n_tf_e, 1)][:n_tf_e]
+        self.aux_f_ptr, self.aux_f_idx = bufs.aux_f_ptr[:n_agg + 1], bufs.aux_f_idx[:max(n_agg_e, 1)][:n_agg_e]
+        self.aux_b_ptr, self.aux_b_idx = bufs.aux_b_ptr[:n_tf + 1], bufs.aux_b_idx[:max(n_tf_e, 1)][:n_tf_e]
         n_f = (E - n_agg_e) + n_agg + (N if self_loop else 0)      # forward list entries; the rest sits in the discard segment
         n_b = (E - n_tf_e) + n_tf + (N if self_loop else 0)
-        self.dst_ptr, self.dst_rows = dst_ptr[:N + 1], dst_rows[:n_f]
-        self.src_ptr, self.src_rows = src_ptr[:N + 1], src_rows[:n_b]
-        self.row_in, self.row_out = row_in[:P_all], row_out[:P_all]
+        self.dst_ptr, self.dst_rows = bufs.dst_ptr[:N + 1], bufs.dst_rows[:n_f]
+        self.src_ptr, self.src_rows = bufs.src_ptr[:N + 1], bufs.src_rows[:n_b]
+        self.row_in, self.row_out = bufs.row_in[:P_all], bufs.row_out[:P_all]
         self.num_rows, self.num_edge_rows = P_all, P
         self.num_all_rels = R + (1 if self_loop else 0)
         self.rel_ptr_host = rel_ptr
         # tile / chunk tables on the device (the 18 relation offsets go up in one small copy; no host loops)
         if self.built_by == "local":                                 # (already on the device: no upload)
-            rel_ptr_d = rel_dev[:len(rel_ptr)]
+            self.rel_ptr_dev = bufs.rel_dev[:len(rel_ptr)]
         else:
-            rel_ptr_d = torch.tensor(rel_ptr, dtype=I32).to(dev, non_blocking=True)
-        self.rel_ptr_dev = rel_ptr_d                                # (reused by the fold tables: one upload per batch)
+            self.rel_ptr_dev = torch.tensor(rel_ptr, dtype=I32).to(self.row_in.device, non_blocking=True)
+        #                                                              (reused by the fold tables: one upload per batch)
         self._tile_table = self._edge_tile_table = None             # built on first use: the folded bf16 path needs neither
         self._slots, self._units, self._fold = {}, {}, {}
-        # one workgroup per CU (the LDS-DMA ring fills a CU's LDS) for the split-K weight gradient whatever the batch size:
-        # the smallest chunk that keeps ALL relations' chunks (each relation ends in a partial one) within one round of 256
-        if pre is not None:
-            self.chunk_table = pre[2]
-            if pre[3] and pre[4]:                                    # both directions served: nothing is left for the first step
-                cands = {d: _fold_candidate(self, d) for d in ("f", "b")}
-                assert cands["f"] is not None and cands["b"] is not None and cands["f"][3] == cands["b"][3] == G
-                for k, d in enumerate(("f", "b")):
-                    info = _make_fold_info(self, d, cands[d])
-                    if pre[3 + k] == 2:                              # a graph over 32 nodes: the call left the chunked form behind
-                        ct, cg, tpm, fim = pre[5](k)
-                        info.graph_tiles = (tpm, fim)
-                        info.multi = (ct, cg, pre[6], G)
-                        pre[0][k].order, pre[0][k].num_tiles = 2 + _close_order(pre[0][k].num_wg), pre[6]
-                    else:
-                        info.graph_tiles = (self._absorb[d][0], self._absorb[d][1])
-                    if pre[1][k] is not None and _sweep_wanted(self):
-                        info.sweep_tiles = pre[1][k]
-                    self._fold[d] = info
-                    self._units[d] = pre[0][k]
-        else:
-            self.chunk_table = build_row_tables(rel_ptr_d, self.num_all_rels, P_all, wgrad_chunk_rows(rel_ptr), want_ptr=True)
+        self.dirs = {"f": RowDirection(self.aux_f_ptr, self.aux_f_idx, n_agg, self.row_in, self.row_out, self.dst_ptr, self.dst_rows),
+                     "b": RowDirection(self.aux_b_ptr, self.aux_b_idx, n_tf, self.row_out, self.row_in, self.src_ptr, self.src_rows)}
 
+    @property
+    def tile_table(self):
+        """Tile table of ALL rows (the self loop as relation R): the path without the fused closing launch."""
+        if self._tile_table is None:
+            self._tile_table = build_row_tables(self.rel_ptr_dev, self.num_all_rels, self.num_rows, 32)
+        return self._tile_table
 
-def _conv_tiles(ix, fold, xs):
-    """Tile table of the edge rows (minus the folded relation) for the conv's transform launch: the L2-blocked sweep order when
-    the persistent H = 256 bf16 launch will walk it and the batch is large enough for the order to matter (built once per
-    index and direction, on first use), else the plain relation-major tiles."""
-    return _conv_tiles_for(ix, fold, xs.shape[1], xs.dtype)
+    @property
+    def edge_tile_table(self):
+        """Tile table of the edge rows (relations 0 .. R-1): closing launch without a folded relation."""
+        if not self.self_loop:
+            return self.tile_table
+        if self._edge_tile_table is None:
+            self._edge_tile_table = build_row_tables(self.rel_ptr_dev, self.num_rels, self.num_edge_rows, 32)
+        return self._edge_tile_table
+
+    def slots(self, direction):
+        """Slot tables for the fused closing launch ('f': rows into each destination, 'b': rows out of each source).
+        The rows of a FOLDED relation (_row_index_fold) are left out: they are added by the tail launches."""
+        _closing_tables(self, "slots")
+        return self._slots[direction]
+
+    def close_units(self, direction):
+        """The same lists as the unit stream of dn_rows_close_bf16 (H = 256)."""
+        _closing_tables(self, "units")
+        return self._units[direction]
+
+    def _adopt_plan(self, plan):
+        """The one-call plan as the index's own tables: the chunk table always; the fold verdicts (_fold) and unit streams (_units)
+        where the call served BOTH directions -- nothing is then left for the first step."""
+        self.chunk_table = plan.chunk_table
+        if not (plan.served[0] and plan.served[1]):
+            return
+        G = int(self.raw[3].numel()) - 1
+        cands = {d: _fold_candidate(self, d) for d in ("f", "b")}
+        assert cands["f"] is not None and cands["b"] is not None and cands["f"][3] == cands["b"][3] == G
+        for k, d in enumerate(("f", "b")):
+            info, cu = _Fold(self, d, cands[d]), plan.units[k]
+            if plan.served[k] == 2:                                  # a graph over 32 nodes: the call left the chunked form behind
+                ct, cg, tpm, fim = plan.multi_views(k)
+                info.graph_tiles = (tpm, fim)
+                info.multi = (ct, cg, plan.multi_tiles, G)
+                cu.order, cu.num_tiles = 2 + _close_order(cu.num_wg), plan.multi_tiles
+            else:
+                info.graph_tiles = (self._absorb[d].tile_ptr, self._absorb[d].fold_info)
+            if plan.sweeps[k] is not None and _sweep_wanted(self):
+                info.sweep_tiles = plan.sweeps[k]
+            self._fold[d] = info
+            self._units[d] = cu
 
 
 def _sweep_wanted(ix):
@@ -1542,6 +1611,9 @@ def _sweep_wanted(ix):
 
 
 def _conv_tiles_for(ix, fold, H, dtype):
+    """Tile table of the edge rows (minus the folded relation) for the conv's transform launch: the L2-blocked sweep order when
+    the persistent H = 256 bf16 launch will walk it and the batch is large enough for the order to matter (built once per
+    index and direction, on first use), else the plain relation-major tiles."""
     P, R = ix.num_edge_rows, ix.num_rels
     if not (dtype == torch.bfloat16 and H == 256 and _sweep_wanted(ix)):
         if fold.main_tiles is None:                                  # (built on first use: a batch on the sweep order never needs them)
@@ -1556,38 +1628,17 @@ def prepare_closing(ix, H, dtype):
     """Every table message_pass would build lazily on a batch's first step -- the closing tables of both directions (slot tables
     or unit streams, fold tables) and the sweep tile orders -- so that a loop can account the per-batch index cost outside the
     step (bench.py's index_build_ms, the overlapped fresh-batch leg)."""
-    kind = "units" if (CLOSE_RING_ENABLED and H == 256 and dtype == torch.bfloat16) else "slots"
-    _closing_tables(ix, kind)
+    _closing_tables(ix, _close_kind(H, dtype))
     for d in ("f", "b"):
         if ix._fold[d] is not None:
             _conv_tiles_for(ix, ix._fold[d], H, dtype)
-
-
-def _row_index_tile_table(ix):
-    """Tile table of ALL rows (the self loop as relation R): the path without the fused closing launch."""
-    if ix._tile_table is None:
-        ix._tile_table = build_row_tables(ix.rel_ptr_dev, ix.num_all_rels, ix.num_rows, 32)
-    return ix._tile_table
-
-
-def _row_index_edge_tile_table(ix):
-    """Tile table of the edge rows (relations 0 .. R-1): closing launch without a folded relation."""
-    if not ix.self_loop:
-        return _row_index_tile_table(ix)
-    if ix._edge_tile_table is None:
-        ix._edge_tile_table = build_row_tables(ix.rel_ptr_dev, ix.num_rels, ix.num_edge_rows, 32)
-    return ix._edge_tile_table
-
-
-RowIndex.tile_table = property(_row_index_tile_table)
-RowIndex.edge_tile_table = property(_row_index_edge_tile_table)
 
 
 def _fold_candidate(ix, direction):
     """(relation, first row, end row, #aux lists) of the one collapsed relation whose pre-aggregation the closing launch could
     absorb in this direction (AGG forward / TF backward), or None -- decided from what the host already knows."""
     mode = RowIndex.AGG if direction == "f" else RowIndex.TF
-    n_aux = ix.num_aux_f if direction == "f" else ix.num_aux_b
+    n_aux = ix.dirs[direction].n_aux
     rels = [r for r, m in enumerate(ix.modes) if m == mode and ix.rel_ptr_host[r + 1] > ix.rel_ptr_host[r]]
     if not (FOLD_ENABLED and ix.self_loop and len(rels) == 1 and ix.num_rels <= 64 and n_aux > 0):
         return None
@@ -1602,31 +1653,17 @@ CLOSE_AGG_ENABLED = _os.environ.get("DN_CLOSE_AGG", "1") != "0"
 
 def _fold_add_idx(ix, direction, cand):
     """The node every segment's product is added to: the folded relation's rows' outputs (forward) / inputs (backward)."""
-    return (ix.row_out if direction == "f" else ix.row_in)[cand[1]:cand[2]].contiguous()
-
-
-def _make_fold_info(ix, direction, cand):
-    r, beg, end, n_aux = cand
-    info = _Fold()
-    info.rel, info.beg, info.end, info.n = r, beg, end, n_aux
-    info.fold_info = info.part_ptr = info.graph_tiles = info.multi = None
-    info.num_parts = int(2 * n_aux + ix.num_nodes // 32 + 1)   # upper bound of part_ptr[-1] without a read-back: every segment
-    #                                                            starts one partial row, every tile boundary inside one another
-    info.main_tiles = None                               # plain relation-major tiles, built on first use (_conv_tiles_for)
-    info.sweep_tiles = None                              # built on the first H = 256 launch (_conv_tiles)
-    info.add_idx = _fold_add_idx(ix, direction, cand)
-    return info
+    return ix.dirs[direction].rows_out[cand[1]:cand[2]].contiguous()
 
 
 def _queue_fold_tables(ix, direction, n_aux, flag):
     """dn_fold_tables_build_async_i32 for one direction (32-node tiles, fp32 partial rows): -> (fold_info, part_ptr); verdict in flag."""
     N, dev = ix.num_nodes, ix.row_in.device
-    aux_ptr, aux_idx = (ix.aux_f_ptr, ix.aux_f_idx) if direction == "f" else (ix.aux_b_ptr, ix.aux_b_idx)
     fold_info = torch.empty(((N + 31) // 32, 12), dtype=I32, device=dev)
     part_ptr = torch.empty(n_aux + 1, dtype=I32, device=dev)
     ws = _ws(lib().dn_fold_tables_workspace_bytes(n_aux), dev)
-    check(lib().dn_fold_tables_build_async_i32(N, n_aux, ptr(aux_ptr), ptr(aux_idx), ptr(fold_info), ptr(part_ptr), ptr(flag),
-                                               ptr(ws), ws.numel(), stream_ptr()), "dn_fold_tables_build_async_i32")
+    check(lib().dn_fold_tables_build_async_i32(N, n_aux, ptr(ix.dirs[direction].aux_ptr), ptr(ix.dirs[direction].aux_idx), ptr(fold_info), ptr(part_ptr),
+                                               ptr(flag), ptr(ws), ws.numel(), stream_ptr()), "dn_fold_tables_build_async_i32")
     return fold_info, part_ptr
 
 
@@ -1641,91 +1678,82 @@ def _late_fold_tables(ix, direction, info):
         raise _lib.DnHipError("fold tables of direction %r are invalid although the graph tiles of the same segments were valid" % direction)
 
 
-def _closing_tables(ix, kind="slots"):
-    """Tables of the closing launches of BOTH directions of a RowIndex.  Every builder leaves its verdict on the device; the host
-    reads the verdicts of both directions in ONE copy (it picks the launch sequence by them).
-      kind "units" (dn_rows_close_bf16, H = 256): first dn_fold_graph_tiles_build_i32 -- are the graphs small enough for the
-        ABSORBED fold? -- one copy; only a direction that fails gets the 32-node-tile fold tables (dn_fold_tables_build_async_i32)
-        and a second copy.  The unit streams are built behind the verdicts (their tiles depend on them).
-      kind "slots" (dn_rows_selfsum_bf16): the fold tables and the slot tables (which read the verdict on the device) are queued
-        in front of the one copy.
-    A second kind on the same index reuses the verdicts and builds only what it misses."""
-    have = ix._slots if kind == "slots" else ix._units
-    if have:
-        return
-    N, P, dev, K = ix.num_nodes, ix.num_edge_rows, ix.row_in.device, SELFSUM_SLOTS
-    first = not ix._fold
-    lists = {d: tuple(t.to(I32).contiguous() for t in ((ix.dst_ptr, ix.dst_rows) if d == "f" else (ix.src_ptr, ix.src_rows)))
-             for d in ("f", "b")}
-    dirs = ("f", "b")
+def _decide_folds(ix, kind, before_readback=None):
+    """The fold of BOTH directions, decided on the first closing kind an index serves: fills ix._fold[d] with the tables of the
+    outcome each direction got (None where there is no candidate or every builder turned it down):
+      absorbed, single tile   every graph within one 32-node tile (kind "units"): the verdict of the graph-local index builder
+                              (ix._absorb), else dn_fold_graph_tiles_build_i32 and one read-back
+      absorbed, multi tile    a graph over 32 nodes whose segments pass the same test without the size limit (kind "units")
+      partial rows            32-node-tile fold tables, fp32 partial rows + dn_fold_tail_bf16 (dn_fold_tables_build_async_i32)
+    before_readback(cands, flags), if given, runs when every builder is queued and before the host reads the last verdicts: the
+    slot tables read theirs on the device."""
+    N, dev, dirs = ix.num_nodes, ix.row_in.device, ("f", "b")
+    cands = {d: _fold_candidate(ix, d) for d in dirs}
+    flags = torch.zeros(4, dtype=I32, device=dev)                    # [parts_f, parts_b, graph_tiles_f, graph_tiles_b]
+    absorb = kind == "units" and CLOSE_AGG_ENABLED
+    single_tiles, single = {}, {d: False for d in dirs}
+    if absorb and ix._absorb is not None:
+        # the graph-local index builder answered "can the fold be absorbed?" itself (same candidate rule, same test) and its
+        # verdicts came back with its one read-back: no launch, no synchronisation here
+        for d in dirs:
+            if cands[d] is not None:
+                a, n = ix._absorb[d], cands[d][3]
+                single_tiles[d] = (a.tile_ptr[:n + 1], a.fold_info[:n])
+                single[d] = bool(a.verdict & 1)
+    elif absorb:
+        for k, d in enumerate(dirs):
+            if cands[d] is not None:
+                single_tiles[d] = build_graph_tiles(ix.dirs[d].aux_ptr[:cands[d][3] + 1].contiguous(), ix.dirs[d].aux_idx, N,
+                                                    ok=flags[2 + k:], add_idx=_fold_add_idx(ix, d, cands[d]))
+        if single_tiles:
+            seen = flags.cpu().tolist()                              # synchronisation 1: can the fold be absorbed?
+            single = {d: cands[d] is not None and seen[2 + k] != 0 for k, d in enumerate(dirs)}
+    if not CLOSE_SINGLE_ENABLED:
+        single = {d: False for d in dirs}
+    need_parts = [d for d in dirs if cands[d] is not None and not single[d]]
+    multi = {}
+    if absorb and CLOSE_MULTI_ENABLED and need_parts:
+        # a graph over 32 nodes: the absorbed fold over MULTI-TILE graphs (every graph's tiles in one workgroup's stream) where the
+        # segments pass the same test without the size limit; one read-back for both directions
+        mflags = torch.zeros(2, dtype=I32, device=dev)
+        for k, d in enumerate(dirs):
+            if d in need_parts:
+                multi[d] = build_graph_tiles_multi(ix.dirs[d].aux_ptr[:cands[d][3] + 1].contiguous(), ix.dirs[d].aux_idx, N,
+                                                   ok=mflags[k:], add_idx=_fold_add_idx(ix, d, cands[d]))
+        seen = mflags.cpu().tolist()
+        multi = {d: multi[d] for k, d in enumerate(dirs) if d in multi and seen[k] != 0}
+        need_parts = [d for d in need_parts if d not in multi]
+    parts = {d: _queue_fold_tables(ix, d, cands[d][3], flags[dirs.index(d):]) for d in need_parts}
+    if before_readback is not None:
+        before_readback(cands, flags)
+    seen = flags.cpu().tolist() if need_parts else [0, 0]         # synchronisation 2 (the only one for kind "slots")
+    parts_valid = {d: d in parts and seen[k] != 0 for k, d in enumerate(dirs)}
+    for d in dirs:
+        info = _Fold(ix, d, cands[d]) if (single[d] or d in multi or parts_valid[d]) else None
+        if single[d]:                                                # absorbed, single tile
+            info.graph_tiles = single_tiles[d]
+        elif d in multi:                                             # absorbed, multi tile
+            info.graph_tiles = (multi[d][0], multi[d][1])
+            info.multi = (multi[d][2], multi[d][3], multi[d][4], cands[d][3])
+        elif parts_valid[d]:                                         # partial rows
+            info.fold_info, info.part_ptr = parts[d]
+        ix._fold[d] = info
 
-    def add_idx_of(direction, cand):
-        return _fold_add_idx(ix, direction, cand)
 
-    def make_info(direction, cand):
-        return _make_fold_info(ix, direction, cand)
-
+def _build_slot_tables(ix):
+    """ix._slots of both directions (dn_rows_selfsum_bf16): on an index's first closing kind the fold tables and the slot tables
+    (which read the fold's verdict on the device) are queued in front of ONE read-back; after the unit streams, a fold absorbed so
+    far gets its partial-row tables first."""
+    N, P, K, dirs = ix.num_nodes, ix.num_edge_rows, SELFSUM_SLOTS, ("f", "b")
+    lists = {d: (ix.dirs[d].list_ptr, ix.dirs[d].list_rows) for d in dirs}
     tabs = {}
-    if first:
-        cands = {d: _fold_candidate(ix, d) for d in dirs}
-        flags = torch.zeros(4, dtype=I32, device=dev)                # [parts_f, parts_b, graph_tiles_f, graph_tiles_b]
-        gts, parts = {}, {}
-        h = hp = [0, 0, 0, 0]
-        if kind == "units" and CLOSE_AGG_ENABLED and ix._absorb is not None:
-            # the graph-local index builder answered "can the fold be absorbed?" itself (same candidate rule, same test) and its
-            # verdicts came back with its one read-back: no launch, no synchronisation here
-            h = [0, 0, 0, 0]
-            for k, d in enumerate(dirs):
-                if cands[d] is not None:
-                    tp, fi, verdict = ix._absorb[d]                      # (bit 0: every block within 32 nodes; bit 1: valid without that limit)
-                    gts[d] = (tp[:cands[d][3] + 1], fi[:cands[d][3]])
-                    h[2 + k] = verdict & 1
-        elif kind == "units" and CLOSE_AGG_ENABLED:
-            for k, d in enumerate(dirs):
-                if cands[d] is not None:
-                    aux_ptr, aux_idx = (ix.aux_f_ptr, ix.aux_f_idx) if d == "f" else (ix.aux_b_ptr, ix.aux_b_idx)
-                    gts[d] = build_graph_tiles(aux_ptr[:cands[d][3] + 1].contiguous(), aux_idx, N, ok=flags[2 + k:],
-                                               add_idx=add_idx_of(d, cands[d]))
-            if gts:
-                h = flags.cpu().tolist()                             # synchronisation 1: can the fold be absorbed?
-        if not CLOSE_SINGLE_ENABLED:
-            h = [h[0], h[1], 0, 0]
-        need_parts = [d for k, d in enumerate(dirs) if cands[d] is not None and h[2 + k] == 0]
-        multi = {}
-        if kind == "units" and CLOSE_AGG_ENABLED and CLOSE_MULTI_ENABLED and need_parts:
-            # a graph over 32 nodes: the absorbed fold over MULTI-TILE graphs (every graph's tiles in one workgroup's stream) where the
-            # segments pass the same test without the size limit; one read-back for both directions
-            mflags = torch.zeros(2, dtype=I32, device=dev)
-            for k, d in enumerate(dirs):
-                if d in need_parts:
-                    aux_ptr, aux_idx = (ix.aux_f_ptr, ix.aux_f_idx) if d == "f" else (ix.aux_b_ptr, ix.aux_b_idx)
-                    multi[d] = build_graph_tiles_multi(aux_ptr[:cands[d][3] + 1].contiguous(), aux_idx, N, ok=mflags[k:],
-                                                       add_idx=add_idx_of(d, cands[d]))
-            hm = mflags.cpu().tolist()
-            multi = {d: multi[d] for k, d in enumerate(dirs) if d in multi and hm[k] != 0}
-            need_parts = [d for d in need_parts if d not in multi]
-        for d in need_parts:
-            parts[d] = _queue_fold_tables(ix, d, cands[d][3], flags[dirs.index(d):])
-        if kind == "slots":
+    if not ix._fold:
+        def queue_slot_tables(cands, flags):
             for k, d in enumerate(dirs):
                 drop, enable = ((cands[d][1], cands[d][2]), flags[k:]) if cands[d] is not None else ((0, 0), None)
                 tabs[d] = build_slot_table(*lists[d], N, P, K, drop=drop, drop_enable=enable)
-        if need_parts:
-            hp = flags.cpu().tolist()                                # synchronisation 2 (the only one for kind "slots")
-        for k, d in enumerate(dirs):
-            info = None
-            if cands[d] is not None and h[2 + k] != 0:
-                info = make_info(d, cands[d])
-                info.graph_tiles = (gts[d][0], gts[d][1])
-            elif d in multi:
-                info = make_info(d, cands[d])
-                info.graph_tiles = (multi[d][0], multi[d][1])
-                info.multi = (multi[d][2], multi[d][3], multi[d][4], cands[d][3])
-            elif cands[d] is not None and hp[k] != 0:
-                info = make_info(d, cands[d])
-                info.fold_info, info.part_ptr = parts[d]
-            ix._fold[d] = info
-    elif kind == "slots":
+        _decide_folds(ix, "slots", before_readback=queue_slot_tables)
+    else:
         for d in dirs:
             info = ix._fold[d]
             if info is not None and info.fold_info is None:          # absorbed so far: the slot kernel needs the partial-row tables
@@ -1733,7 +1761,7 @@ def _closing_tables(ix, kind="slots"):
             drop = (info.beg, info.end) if info is not None else (0, 0)
             tabs[d] = build_slot_table(*lists[d], N, P, K, drop=drop)
     longest = {d: None for d in dirs}
-    if kind == "slots" and 0 < N <= OVERFLOW_INSIDE_MAX_ROWS:
+    if 0 < N <= OVERFLOW_INSIDE_MAX_ROWS:
         # the longest list of each direction (one small read-back per batch, small batches only): rows_selfsum walks overflowing
         # lists inside the launch only while they are short
         mx = torch.stack([(lists[d][0][1:N + 1] - lists[d][0][:N]).max() for d in dirs]).tolist()
@@ -1741,36 +1769,42 @@ def _closing_tables(ix, kind="slots"):
     for d in dirs:
         info = ix._fold[d]
         drop = (info.beg, info.end) if info is not None else (0, 0)
-        if (kind == "units" and info is not None and info.graph_tiles is None and CLOSE_AGG_ENABLED and CLOSE_SINGLE_ENABLED
-                and ix._absorb is not None and (ix._absorb[d][2] & 1)):                                # (the slot tables came first: the builder's verdict still stands)
-            info.graph_tiles = (ix._absorb[d][0][:info.n + 1], ix._absorb[d][1][:info.n])
-        if kind == "slots":
-            slots, over = tabs[d]
-            ix._slots[d] = (slots, (*lists[d], P, drop[0], drop[1], over, longest[d]))
-        elif info is not None and info.graph_tiles is not None:     # every graph inside one tile: the fold is absorbed
-            ix._units[d] = build_close_units(*lists[d], N, P, drop=drop, tile_ptr=info.graph_tiles[0], agg=True, multi=info.multi)
+        slots, over = tabs[d]
+        ix._slots[d] = (slots, (*lists[d], P, drop[0], drop[1], over, longest[d]))
+
+
+def _build_unit_streams(ix):
+    """ix._units of both directions (dn_rows_close_bf16, H = 256), built behind the fold's verdicts: their tiles depend on them."""
+    N, P = ix.num_nodes, ix.num_edge_rows
+    if not ix._fold:
+        _decide_folds(ix, "units")
+    for d in ("f", "b"):
+        info, lists = ix._fold[d], (ix.dirs[d].list_ptr, ix.dirs[d].list_rows)
+        drop = (info.beg, info.end) if info is not None else (0, 0)
+        if (info is not None and info.graph_tiles is None and CLOSE_AGG_ENABLED and CLOSE_SINGLE_ENABLED
+                and ix._absorb is not None and (ix._absorb[d].verdict & 1)):     # (the slot tables came first: the builder's verdict still stands)
+            info.graph_tiles = (ix._absorb[d].tile_ptr[:info.n + 1], ix._absorb[d].fold_info[:info.n])
+        if info is not None and info.graph_tiles is not None:       # every graph inside one tile: the fold is absorbed
+            ix._units[d] = build_close_units(*lists, N, P, drop=drop, tile_ptr=info.graph_tiles[0], agg=True, multi=info.multi)
         else:
             if info is not None and info.fold_info is None:
                 _late_fold_tables(ix, d, info)
-            ix._units[d] = build_close_units(*lists[d], N, P, drop=drop)
+            ix._units[d] = build_close_units(*lists, N, P, drop=drop)
 
 
-def _row_index_slots(ix, direction):
-    """Slot tables of a RowIndex for the fused closing launch ('f': rows into each destination, 'b': rows out of each source).
-    The rows of a FOLDED relation (_row_index_fold) are left out: they are added by the tail launches."""
-    _closing_tables(ix, "slots")
-    return ix._slots[direction]
+def _closing_tables(ix, kind="slots"):
+    """Tables of the closing launches of BOTH directions of a RowIndex: kind "units" (_build_unit_streams) or "slots"
+    (_build_slot_tables).  The first kind an index serves decides the folds (_decide_folds); a second kind on the same index reuses
+    the verdicts and builds only what it misses."""
+    if kind == "slots" and not ix._slots:
+        _build_slot_tables(ix)
+    elif kind != "slots" and not ix._units:
+        _build_unit_streams(ix)
 
 
-def _row_index_close_units(ix, direction):
-    """The same lists as the unit stream of dn_rows_close_bf16 (H = 256)."""
-    _closing_tables(ix, "units")
-    return ix._units[direction]
-
-
-def _close_kind(x):
+def _close_kind(H, dtype):
     """Which closing launch serves rows of this width: the unit stream (H = 256) or the slot kernel."""
-    return "units" if (CLOSE_RING_ENABLED and x.shape[1] == 256 and x.dtype == torch.bfloat16) else "slots"
+    return "units" if (CLOSE_RING_ENABLED and H == 256 and dtype == torch.bfloat16) else "slots"
 
 
 # The collapsed relation of a dummy-augmented batch (u -> dummy forward, dummy -> u backward) needs the SUM of a graph's rows as
@@ -1784,6 +1818,15 @@ class _Fold:
     __slots__ = ("rel", "beg", "end", "n", "fold_info", "part_ptr", "num_parts", "main_tiles", "sweep_tiles", "add_idx",
                  "graph_tiles", "multi")
 
+    def __init__(self, ix, direction, cand):
+        self.rel, self.beg, self.end, self.n = cand
+        self.fold_info = self.part_ptr = self.graph_tiles = self.multi = None
+        self.num_parts = int(2 * self.n + ix.num_nodes // 32 + 1)   # upper bound of part_ptr[-1] without a read-back: every segment
+        #                                                             starts one partial row, every tile boundary inside one another
+        self.main_tiles = None                               # plain relation-major tiles, built on first use (_conv_tiles_for)
+        self.sweep_tiles = None                              # built on the first H = 256 launch (_conv_tiles_for)
+        self.add_idx = _fold_add_idx(ix, direction, cand)
+
 
 def _row_index_fold(ix, direction, kind="slots"):
     """The relation whose pre-aggregation the closing launch can absorb, or None: exactly ONE collapsed relation in this
@@ -1793,23 +1836,20 @@ def _row_index_fold(ix, direction, kind="slots"):
     return ix._fold[direction]
 
 
-RowIndex.slots = _row_index_slots
-RowIndex.close_units = _row_index_close_units
-
-
 class RowIndexSet:
-    """Holder of a batch's RowIndex (`parts` = [(first node, end node, RowIndex)], one part) and of the Y buffer its launches
-    share.  (Rounds 1-2 could cut a batch into cache-resident sub-batches here; under-filled launches lost more than the
-    Infinity Cache returned at every split -- DESIGN.md section 4 -- and the splitting was removed in round 3.)"""
+    """Holder of a batch's ONE RowIndex (`index`) and of the Y buffers its launches share.  `parts` = [(0, N, index)] is the form
+    the benchmark and the tools read.  (Cutting a batch into cache-resident sub-batches lost more to under-filled launches than the
+    Infinity Cache returned at every split -- DESIGN.md section 4.)"""
 
-    def __init__(self, src, dst, etype, num_nodes, num_rels, self_loop, node_ptr=None, edge_ptr=None, closing_hint=None):
-        N = int(num_nodes)
-        self.num_nodes, self.num_rels, self.self_loop = N, int(num_rels), bool(self_loop)
-        self.parts = [(0, N, RowIndex(src, dst, etype, N, num_rels, self_loop=self_loop, node_ptr=node_ptr, edge_ptr=edge_ptr,
-                                      closing_hint=closing_hint))]
-        self.max_rows = max(ix.num_rows for _, _, ix in self.parts)
-        self.num_rows = sum(ix.num_rows for _, _, ix in self.parts)
-        self.num_all_rels = self.num_rels + (1 if self_loop else 0)
+    def __init__(self, src=None, dst=None, etype=None, num_nodes=None, num_rels=None, self_loop=None, node_ptr=None, edge_ptr=None,
+                 closing_hint=None, index=None):
+        """RowIndexSet(index=ix) holds a RowIndex that exists already; else the index is built from the batch."""
+        self.index = ix = index if index is not None else RowIndex(
+            src, dst, etype, int(num_nodes), num_rels, self_loop=self_loop, node_ptr=node_ptr, edge_ptr=edge_ptr, closing_hint=closing_hint)
+        self.num_nodes, self.num_rels, self.self_loop = ix.num_nodes, ix.num_rels, ix.self_loop
+        self.parts = [(0, ix.num_nodes, ix)]
+        self.max_rows = self.num_rows = ix.num_rows
+        self.num_all_rels = ix.num_all_rels
         self._ybuf = {}
 
     def ybuf(self, H, dtype, dev):
@@ -1838,10 +1878,7 @@ def fold_tail(part, part_ptr, num_segments, Wn, idx, out, w_kn=False):
     def _launch():
         check(lib().dn_fold_tail_bf16(ptr(part), ptr(part_ptr), int(num_segments), H, ptr(Wn), ptr(idx), ptr(aux), ptr(out),
                                       1 if w_kn else 0, stream_ptr()), "dn_fold_tail_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("fold_tail", _launch)
-    else:
-        _launch()
+    launch_tagged("fold_tail", _launch)
     return aux
 
 
@@ -1889,7 +1926,7 @@ def _kn_ok(xs):
 def _closing_launch(xs, W_loop, bias, Y, ix, direction, out, seg=None, w_kn=False):
     """The closing launch over one RowIndex: the unit stream at H = 256 (dn_rows_close_bf16), else the slot kernel + its
     overflow launch (dn_rows_selfsum_bf16, dn_overflow_rows_add_bf16)."""
-    if _close_kind(xs) == "units":
+    if _close_kind(xs.shape[1], xs.dtype) == "units":
         return rows_close(xs, W_loop, bias, Y, ix.close_units(direction), out=out, seg=seg, w_kn=w_kn)
     slots, lists = ix.slots(direction)
     return rows_selfsum(xs, W_loop, bias, Y, None, slots, out=out, seg=seg, lists=lists, w_kn=w_kn)
@@ -1901,10 +1938,10 @@ def _message_pass_folded(xs, pw, bias, ix, direction, ybuf, out, idx_rows):
     add each product to its node).  Where every graph fits one tile of the unit stream (H = 256) the closing launch does the
     tail's work itself (its AGG units): two launches per direction.  Same sums as the unfolded path up to bf16 rounding of the
     collapsed rows."""
-    kind = _close_kind(xs)
+    kind = _close_kind(xs.shape[1], xs.dtype)
     fold = _row_index_fold(ix, direction, kind)
     P, H = ix.num_edge_rows, xs.shape[1]
-    Y = rows_transform(xs, pw.rel, _conv_tiles(ix, fold, xs), P, idx=idx_rows, tag="conv", out=ybuf, w_kn=pw.kn)
+    Y = rows_transform(xs, pw.rel, _conv_tiles_for(ix, fold, H, xs.dtype), P, idx=idx_rows, tag="conv", out=ybuf, w_kn=pw.kn)
     if kind == "units" and ix.close_units(direction).agg:
         aux = torch.empty((fold.n, H), dtype=xs.dtype, device=xs.device)
         rows_close(xs, pw.loop, bias, Y[:P], ix.close_units(direction), out=out, w_kn=pw.kn,
@@ -1934,41 +1971,41 @@ def conv_graphs(xs, pw, bias, ix, direction, out):
     by the same launch where the direction's aux lists are the graphs' segments; else one gather launch)."""
     src, dst, etype, node_ptr, edge_ptr = ix.raw
     key_in, key_out = (src, dst) if direction == "f" else (dst, src)
-    aux_idx, aux_ptr, n_aux = (ix.aux_f_idx, ix.aux_f_ptr, ix.num_aux_f) if direction == "f" else (ix.aux_b_idx, ix.aux_b_ptr, ix.num_aux_b)
+    v = ix.dirs[direction]
     G, N, H = int(node_ptr.numel()) - 1, ix.num_nodes, 64
     require_gpu(xs, pw.rel, pw.loop, bias, out)
     assert xs.is_contiguous() and out.is_contiguous() and out.shape == xs.shape and pw.rel.is_contiguous() and pw.loop.is_contiguous()
-    if getattr(ix, "_cg_err", None) is None:
-        ix._cg_err = torch.zeros(16, dtype=I32, device=xs.device)
-    cand = _fold_candidate(ix, direction) if n_aux else None
-    inside = (cand is not None and cand[3] == G and n_aux == G and ix._absorb is not None and ix._absorb[direction][2] != 0)
-    aux = torch.empty((n_aux, H), dtype=xs.dtype, device=xs.device) if inside else None
-    sp = aux_ptr[:n_aux + 1].contiguous() if inside else None
+    err = _graphs_err(ix, xs.device)
+    inside, aux, sp, sn = _graphs_aux(ix, direction, xs)
 
     def _launch():
         check(lib().dn_conv_graphs_bf16(ptr(xs), H, ptr(pw.rel), 1 if pw.kn else 0, ptr(pw.loop), ptr(bias), ix.num_rels, ptr(node_ptr),
                                         ptr(edge_ptr), ptr(key_in), ptr(key_out), ptr(etype), G, N, ptr(out), ptr(sp),
-                                        ptr(aux_idx) if inside else None, ptr(aux), ptr(ix._cg_err), stream_ptr()),
+                                        ptr(sn), ptr(aux), ptr(err), stream_ptr()),
               "dn_conv_graphs_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("conv_graphs", _launch)
-    else:
-        _launch()
-    if n_aux and not inside:
-        aux = gather_segsum(xs, aux_idx, aux_ptr, n_aux)
+    launch_tagged("conv_graphs", _launch)
+    if v.n_aux and not inside:
+        aux = gather_segsum(xs, v.aux_idx, v.aux_ptr, v.n_aux)
     return aux
+
+
+def _graphs_err(ix, dev):
+    """The error / statistics words the whole-graph launches of an index OR into (one buffer per index, made on first use)."""
+    if ix._cg_err is None:
+        ix._cg_err = torch.zeros(16, dtype=I32, device=dev)
+    return ix._cg_err
 
 
 def _graphs_aux(ix, direction, xs):
     """(inside, aux tensor or None, seg_ptr or None, seg_nodes or None) for the whole-graph launches: the direction's aux lists are the
     graphs' segments (one collapsed relation, one row per graph) -> the launch writes the column sums itself."""
-    aux_idx, aux_ptr, n_aux = (ix.aux_f_idx, ix.aux_f_ptr, ix.num_aux_f) if direction == "f" else (ix.aux_b_idx, ix.aux_b_ptr, ix.num_aux_b)
+    v = ix.dirs[direction]
     G = int(ix.raw[3].numel()) - 1
-    cand = _fold_candidate(ix, direction) if n_aux else None
-    inside = (cand is not None and cand[3] == G and n_aux == G and ix._absorb is not None and ix._absorb[direction][2] != 0)
+    cand = _fold_candidate(ix, direction) if v.n_aux else None
+    inside = (cand is not None and cand[3] == G and v.n_aux == G and ix._absorb is not None and ix._absorb[direction].verdict != 0)
     if not inside:
         return False, None, None, None
-    return True, torch.empty((n_aux, xs.shape[1]), dtype=xs.dtype, device=xs.device), aux_ptr[:n_aux + 1].contiguous(), aux_idx
+    return True, torch.empty((v.n_aux, xs.shape[1]), dtype=xs.dtype, device=xs.device), v.aux_ptr[:v.n_aux + 1].contiguous(), v.aux_idx
 
 
 def layer_graphs_fwd(x, W, W_loop, bias, w1, b1, w2, b2, slope, ix):
@@ -1978,8 +2015,7 @@ def layer_graphs_fwd(x, W, W_loop, bias, w1, b1, w2, b2, slope, ix):
     G, N, H = int(node_ptr.numel()) - 1, ix.num_nodes, 64
     require_gpu(x, W, W_loop, bias, w1, b1, w2, b2)
     assert x.is_contiguous() and W.is_contiguous() and W_loop.is_contiguous() and w1.is_contiguous() and w2.is_contiguous()
-    if getattr(ix, "_cg_err", None) is None:
-        ix._cg_err = torch.zeros(16, dtype=I32, device=x.device)
+    err = _graphs_err(ix, x.device)
     inside, aux, sp, sn = _graphs_aux(ix, "f", x)
     h, h1, h2 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     bits1 = torch.empty((N, H // 8), dtype=torch.uint8, device=x.device)
@@ -1988,12 +2024,9 @@ def layer_graphs_fwd(x, W, W_loop, bias, w1, b1, w2, b2, slope, ix):
     def _launch():
         check(lib().dn_layer_graphs_fwd_bf16(ptr(x), H, ptr(W), ptr(W_loop), ptr(bias), ix.num_rels, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
                                              float(slope), ptr(node_ptr), ptr(edge_ptr), ptr(src), ptr(dst), ptr(etype), G, N, ptr(h), ptr(h1),
-                                             ptr(h2), ptr(bits1), ptr(bits2), ptr(sp), ptr(sn), ptr(aux), ptr(ix._cg_err), stream_ptr()),
+                                             ptr(h2), ptr(bits1), ptr(bits2), ptr(sp), ptr(sn), ptr(aux), ptr(err), stream_ptr()),
               "dn_layer_graphs_fwd_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("layer_graphs_fwd", _launch)
-    else:
-        _launch()
+    launch_tagged("layer_graphs_fwd", _launch)
     if ix.num_aux_f and not inside:
         aux = gather_segsum(x, ix.aux_f_idx, ix.aux_f_ptr, ix.num_aux_f)
     return h, h1, h2, bits1, bits2, aux
@@ -2013,10 +2046,7 @@ def layer_graphs_bwd(g, W, W_loop, w1, w2, slope, bits1, bits2, ix):
                                              ptr(bits2), ptr(node_ptr), ptr(edge_ptr), ptr(src), ptr(dst), ptr(etype), G, N, ptr(g1), ptr(g0),
                                              ptr(gx), ptr(sp), ptr(sn), ptr(aux_b), ptr(ix._cg_err), stream_ptr()),
               "dn_layer_graphs_bwd_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("layer_graphs_bwd", _launch)
-    else:
-        _launch()
+    launch_tagged("layer_graphs_bwd", _launch)
     if ix.num_aux_b and not inside:
         aux_b = gather_segsum(g0, ix.aux_b_idx, ix.aux_b_ptr, ix.num_aux_b)
     return g1, g0, gx, aux_b
@@ -2030,22 +2060,19 @@ def message_pass(xs, pw, bias, ix, direction, ybuf, out, add_in=None):
        closing launch.  With a self loop in bf16 the closing launch is dn_rows_close_bf16 / dn_rows_selfsum_bf16 (self-loop
        transform + bias + per-node sum of the edge rows in one pass); otherwise the self-loop rows go through the transform like
        any relation and a per-node gather_segsum closes.  Returns the pre-aggregated rows (kept for the weight gradient)."""
-    if direction == "f":
-        aux_idx, aux_ptr, n_aux, idx_rows, lst, lptr = ix.aux_f_idx, ix.aux_f_ptr, ix.num_aux_f, ix.row_in, ix.dst_rows, ix.dst_ptr
-    else:
-        aux_idx, aux_ptr, n_aux, idx_rows, lst, lptr = ix.aux_b_idx, ix.aux_b_ptr, ix.num_aux_b, ix.row_out, ix.src_rows, ix.src_ptr
+    v = ix.dirs[direction]
     f32_direct = xs.dtype == torch.float32 and _kn_ok(xs) and pw.rel.shape[1] == pw.rel.shape[2]
     assert add_in is None or f32_direct        # (add_in: rows added to the result by the closing gather -- the fp32 path only)
     if conv_graphs_ok(xs, pw, ix):
         return conv_graphs(xs, pw, bias, ix, direction, out)
     if pw.kn and not (f32_direct or (_kn_ok(xs) and _selfsum_ok(ix, xs))):
         pw = pw.nk()
-    if _selfsum_ok(ix, xs) and _row_index_fold(ix, direction, _close_kind(xs)) is not None:
-        return _message_pass_folded(xs, pw, bias, ix, direction, ybuf, out, idx_rows)
-    aux = gather_segsum(xs, aux_idx, aux_ptr, n_aux) if n_aux else None
+    if _selfsum_ok(ix, xs) and _row_index_fold(ix, direction, _close_kind(xs.shape[1], xs.dtype)) is not None:
+        return _message_pass_folded(xs, pw, bias, ix, direction, ybuf, out, v.rows_in)
+    aux = gather_segsum(xs, v.aux_idx, v.aux_ptr, v.n_aux) if v.n_aux else None
     if _selfsum_ok(ix, xs):
         P = ix.num_edge_rows
-        Y = (rows_transform(xs, pw.rel, ix.edge_tile_table, P, idx=idx_rows, X2=aux, tag="conv", out=ybuf, w_kn=pw.kn)
+        Y = (rows_transform(xs, pw.rel, ix.edge_tile_table, P, idx=v.rows_in, X2=aux, tag="conv", out=ybuf, w_kn=pw.kn)
              if P else ybuf[:0])
         _closing_launch(xs, pw.loop, bias, Y[:P], ix, direction, out, w_kn=pw.kn)
         return aux
@@ -2053,23 +2080,23 @@ def message_pass(xs, pw, bias, ix, direction, ybuf, out, add_in=None):
         # fp32: the transform reads weight / loop_weight / h_bias where the parameters lie (no cat, no transposed copy, no padded
         # bias matrix); the self-loop rows are relation R of the tile table
         R = pw.rel.shape[0]
-        Y = rows_transform(xs, pw.rel, ix.tile_table, ix.num_rows, idx=idx_rows, X2=aux, bias=bias, tag="conv", out=ybuf,
+        Y = rows_transform(xs, pw.rel, ix.tile_table, ix.num_rows, idx=v.rows_in, X2=aux, bias=bias, tag="conv", out=ybuf,
                            w_kn=pw.kn, W_loop=pw.loop, loop_rel=R, bias_rel=R if bias is not None else -1)
-        gather_segsum(Y, lst, lptr, ix.num_nodes, out=out, self_in=add_in, self_coef=1.0 if add_in is not None else 0.0)
+        gather_segsum(Y, v.list_rows, v.list_ptr, ix.num_nodes, out=out, self_in=add_in, self_coef=1.0 if add_in is not None else 0.0)
         return aux
     Wmat = pw.all_nk()
     bias_all = None
     if bias is not None:
         bias_all = torch.zeros((Wmat.shape[0], Wmat.shape[1]), dtype=xs.dtype, device=xs.device)
         bias_all[-1] = bias                                                  # only self-loop rows carry the bias
-    Y = rows_transform(xs, Wmat, ix.tile_table, ix.num_rows, idx=idx_rows, X2=aux, bias=bias_all, tag="conv", out=ybuf)
-    gather_segsum(Y, lst, lptr, ix.num_nodes, out=out)
+    Y = rows_transform(xs, Wmat, ix.tile_table, ix.num_rows, idx=v.rows_in, X2=aux, bias=bias_all, tag="conv", out=ybuf)
+    gather_segsum(Y, v.list_rows, v.list_ptr, ix.num_nodes, out=out)
     return aux
 
 
 class _RowTransformFn(torch.autograd.Function):
     """out = sum over in-edges of x[src] @ W[etype]  (+ x @ W_loop + bias when the index has the self loop), evaluated
-    over the parts of a RowIndexSet (one part).  W [R, in, out] and W_loop [in, out] are the layer's own tensors: nothing is
+    over a RowIndexSet's index.  W [R, in, out] and W_loop [in, out] are the layer's own tensors: nothing is
     concatenated or transposed on the bf16 H = 256 path."""
 
     @staticmethod
@@ -2082,51 +2109,38 @@ class _RowTransformFn(torch.autograd.Function):
             pw = pw.nk()                                                     # [R', out, in], one cat + transposed copy
         out = torch.empty((x.shape[0], H_out), dtype=x.dtype, device=x.device)
         ybuf = index_set.ybuf(H_out, x.dtype, x.device)
-        auxs = []
-        for n0, n1, ix in index_set.parts:
-            aux = message_pass(x[n0:n1], pw, bias, ix, "f", ybuf, out[n0:n1])
-            auxs.append(aux if aux is not None else x.new_empty(0))      # a few MB: kept for the weight gradient
+        aux = message_pass(x, pw, bias, index_set.index, "f", ybuf, out)
         ctx.index_set, ctx.has_bias, ctx.has_loop = index_set, bias is not None, W_loop is not None
-        ctx.save_for_backward(x, W, W_loop if W_loop is not None else x.new_empty(0), *auxs)
+        ctx.save_for_backward(x, W, W_loop if W_loop is not None else x.new_empty(0),
+                              aux if aux is not None else x.new_empty(0))    # a few MB: kept for the weight gradient
         return out
 
     @staticmethod
     @_backward_in_forward_mode
     def backward(ctx, g):
-        iset = ctx.index_set
+        iset, ix = ctx.index_set, ctx.index_set.index
         g = g.contiguous()
-        x, W, W_loop = ctx.saved_tensors[:3]
-        auxs = ctx.saved_tensors[3:]
+        x, W, W_loop, aux = ctx.saved_tensors
         R_all = W.shape[0] + (1 if ctx.has_loop else 0)
         pw = PassWeights(W, W_loop if ctx.has_loop else None, kn=False)     # the input-gradient pass reads W as it is
         need_x = ctx.needs_input_grad[0]
         need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3])
         gx = torch.empty_like(x) if need_x else None
-        gW32 = cs32 = None
-        ybuf = iset.ybuf(W.shape[1], g.dtype, g.device)
-        single = len(iset.parts) == 1
-        for part, (n0, n1, ix) in enumerate(iset.parts):
-            gs, xs = g[n0:n1], x[n0:n1]
-            if need_x:
-                aux_b = message_pass(gs, pw, None, ix, "b", ybuf, gx[n0:n1])
-            else:
-                aux_b = gather_segsum(gs, ix.aux_b_idx, ix.aux_b_ptr, ix.num_aux_b) if ix.num_aux_b else None
-            if need_w:
-                aux = auxs[part] if ix.num_aux_f else None
-                # bias gradient = column sum of g over the self-loop rows (one per node), folded into the same kernel
-                gw, cs = rows_wgrad(xs, gs, ix.chunk_table, R_all, idx_a=ix.row_in, idx_g=ix.row_out, A2=aux,
-                                    G2=aux_b, out_dtype=W.dtype if single else torch.float32, colsum_of=2, colsum_lp=single,
-                                    colsum_rel=R_all - 1)                  # (gb = cs32[-1] below: the other relations' sums are not used)
-                gW32 = gw if gW32 is None else gW32.add_(gw)
-                cs32 = cs if cs32 is None else cs32.add_(cs)
+        if need_x:
+            aux_b = message_pass(g, pw, None, ix, "b", iset.ybuf(W.shape[1], g.dtype, g.device), gx)
+        else:
+            aux_b = gather_segsum(g, ix.aux_b_idx, ix.aux_b_ptr, ix.num_aux_b) if ix.num_aux_b else None
         gW = gL = gb = None
         if need_w:
-            gAll = gW32.to(W.dtype)                                          # [R (+1), in, out]: the two gradients are views of it
-            gW = gAll[:W.shape[0]]
+            # bias gradient = column sum of g over the self-loop rows (one per node), folded into the same kernel
+            gAll, cs = rows_wgrad(x, g, ix.chunk_table, R_all, idx_a=ix.row_in, idx_g=ix.row_out, A2=aux if ix.num_aux_f else None,
+                                  G2=aux_b, out_dtype=W.dtype, colsum_of=2, colsum_lp=True,
+                                  colsum_rel=R_all - 1)                      # (gb = cs[-1] below: the other relations' sums are not used)
+            gW = gAll[:W.shape[0]]                                           # [R (+1), in, out]: the two gradients are views of it
             if ctx.has_loop:
                 gL = gAll[W.shape[0]]
             if ctx.has_bias:
-                gb = cs32[-1].to(g.dtype)
+                gb = cs[-1].to(g.dtype)
         return gx, gW, gL, gb, None
 
 
@@ -2170,11 +2184,7 @@ def rel_transform_fused(x, W, bias, index_set, W_loop=None):
     layer's own parameters, nothing concatenated), or, without W_loop, W = [R (+1), in, out] with the self-loop weight LAST when
     index_set.self_loop.  bias is added on the self-loop rows (requires the self loop).  index_set: RowIndexSet (or a RowIndex)."""
     if isinstance(index_set, RowIndex):
-        one = index_set
-        index_set = RowIndexSet.__new__(RowIndexSet)
-        index_set.num_nodes, index_set.num_rels, index_set.self_loop = one.num_nodes, one.num_rels, one.self_loop
-        index_set.parts, index_set.max_rows, index_set.num_rows = [(0, one.num_nodes, one)], one.num_rows, one.num_rows
-        index_set.num_all_rels, index_set._ybuf = one.num_all_rels, {}
+        index_set = RowIndexSet(index=index_set)
     assert bias is None or index_set.self_loop
     if W_loop is None and index_set.self_loop:
         assert W.shape[0] == index_set.num_all_rels
@@ -2302,10 +2312,7 @@ def mlp_bwd_fused(g, a, w, chunk_table, mask_in_bits=None, mask_out_bits=None, s
         check(lib().dn_mlp_bwd_fused_bf16(ptr(g), ptr(a), ptr(w), ptr(mask_in_bits), ptr(mask_out_bits), N, H, ptr(chunks), nchunks,
                                           ptr(chunk_ptr), ptr(gw), 0, ptr(colsum), ptr(gb), ptr(g_next), float(slope), ptr(ws),
                                           ws.numel(), stream_ptr()), "dn_mlp_bwd_fused_bf16")
-    if kernel_timer is not None:
-        kernel_timer.launch("mlp_bwd_fused", _launch)
-    else:
-        _launch()
+    launch_tagged("mlp_bwd_fused", _launch)
     return gw, gb, g_next
 
 
@@ -2436,12 +2443,12 @@ LAYER_SMALL_ENABLED = _os.environ.get("DN_LAYER_SMALL", "1") != "0"
 def rgin_layer_small_ok(x, W, W_loop, bias, linears, index_set):
     """Can a whole RGIN layer (conv + bias + 2-layer MLP + activations) run as _RginLayerSmallFn?  bf16, H = 64, square, self loop,
     two square Linears, a batch dn_conv_graphs_bf16 takes."""
-    if not (LAYER_SMALL_ENABLED and CHAIN2_ENABLED and W_loop is not None and len(linears) == 2 and len(index_set.parts) == 1):
+    if not (LAYER_SMALL_ENABLED and CHAIN2_ENABLED and W_loop is not None and len(linears) == 2):
         return False
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] == 64 and W.dtype == x.dtype
             and all(l.weight.dtype == x.dtype and tuple(l.weight.shape) == (64, 64) for l in linears)):
         return False
-    return conv_graphs_ok(x, PassWeights(W, W_loop, kn=True), index_set.parts[0][2])
+    return conv_graphs_ok(x, PassWeights(W, W_loop, kn=True), index_set.index)
 
 
 class _RginLayerSmallFn(torch.autograd.Function):
@@ -2455,7 +2462,7 @@ class _RginLayerSmallFn(torch.autograd.Function):
     def forward(ctx, x, slope, index_set, W, W_loop, bias, w1, b1, w2, b2):
         ctx.f32_mode = f32_mode()
         x = x.contiguous()
-        ix = index_set.parts[0][2]
+        ix = index_set.index
         if LAYER_GRAPHS_ENABLED:
             h, h1, h2, bits1, bits2, aux = layer_graphs_fwd(x, W.contiguous(), W_loop.contiguous(), bias, w1.contiguous(), b1,
                                                             w2.contiguous(), b2, float(slope), ix)
@@ -2474,7 +2481,6 @@ class _RginLayerSmallFn(torch.autograd.Function):
         ix, slope = ctx.ix, ctx.slope
         x, h, h1, bits1, bits2, W, W_loop, w1, w2, aux = ctx.saved_tensors
         g = gout.contiguous()
-        N, H, R = x.shape[0], 64, W.shape[0]
         if LAYER_GRAPHS_ENABLED:
             g1, g0, gx, aux_b = layer_graphs_bwd(g, W.contiguous(), W_loop.contiguous(), w1.contiguous(), w2.contiguous(), slope, bits1, bits2,
                                                  ix)
@@ -2482,18 +2488,9 @@ class _RginLayerSmallFn(torch.autograd.Function):
             g1, g0 = rows_chain2(g, w2, None, False, w1, None, False, mask0_bits=bits2, mask1_bits=bits1, w_kn=(True, True), slope=slope)
             gx = torch.empty_like(x)
             aux_b = conv_graphs(g0, PassWeights(W, W_loop, kn=False), None, ix, "b", gx)
-        # the conv's rows (relation-major, the self loop as relation R), then the two Linears' dense rows, in one virtual row space
-        if getattr(ix, "_layer_chunks", None) is None:
-            P_all = ix.num_rows
-            vptr_host = list(ix.rel_ptr_host) + [P_all + N, P_all + 2 * N]
-            vptr = torch.cat([ix.rel_ptr_dev[:R + 2], torch.tensor([P_all + N, P_all + 2 * N], dtype=I32, device=x.device)])
-            ix._layer_chunks = build_row_tables(vptr, R + 3, P_all + 2 * N, wgrad_chunk_rows(vptr_host, _SMALL_WG), want_ptr=True)
-        jobs = [dict(A=x, A2=aux if ctx.has[3] else None, idx_a=ix.row_in, G=g0, G2=aux_b, idx_g=ix.row_out, colsum_of=2, first_rel=0, row0=0),
-                dict(A=g1, G=h, colsum_of=1, first_rel=R + 1, row0=ix.num_rows),
-                dict(A=g, G=h1, colsum_of=1, mask_a_bits=bits2, slope=slope, first_rel=R + 2, row0=ix.num_rows + N)]
-        gw, cs = rows_wgrad_multi(jobs, ix._layer_chunks, R + 3, H, W.dtype)
-        return (gx, None, None, gw[:R], gw[R], cs[R] if ctx.has[0] else None, gw[R + 1], cs[R + 1] if ctx.has[1] else None, gw[R + 2],
-                cs[R + 2] if ctx.has[2] else None)
+        grads = layer_wgrad(ix, "small", 64, W.dtype, ctx.has, dict(A=x, A2=aux if ctx.has[3] else None, G=g0, G2=aux_b, colsum_of=2),
+                            dict(A=g1, G=h), dict(A=g, G=h1, mask_a_bits=bits2, slope=slope))
+        return (gx, None, None, *grads)
 
 
 # DN_LAYER_WIDE=0: an H = 256 bf16 RGIN layer stays a chain of separate autograd functions (conv, MLP), three weight-gradient launches
@@ -2538,16 +2535,38 @@ def wide_layer_chunks(rel_ptr_host, n_nodes, device, workgroups=256, dense_weigh
     return ch.to(device), torch.tensor(cptr, dtype=I32).to(device), len(chunks)
 
 
+def layer_wgrad(ix, cut, H, out_dtype, has, conv, lin1, lin2):
+    """The ONE weight-gradient launch of a layer function (rows_wgrad_multi) over the virtual row space of an index with a self loop:
+    the conv's rows (relation-major, the self loop as relation R), then the two Linears' N dense rows each.  conv / lin1 / lin2 = the
+    operands of the three jobs, has = (conv bias?, bias 1?, bias 2?, ...).  -> the gradients of (W, W_loop, bias, w1, b1, w2, b2).
+    The split-K chunk table is built on first use and cached on the index PER CUT ("wide": wide_layer_chunks, H = 256; "small": equal
+    steps for two rounds of workgroups, H = 64 / 128): a graph keeps one index for layers of every width, and a layer must get the
+    table it would build on a fresh index whichever layer touched the batch first."""
+    R, N, P_all, dev = ix.num_rels, ix.num_nodes, ix.num_rows, ix.row_in.device
+    if cut not in ix._layer_chunks and cut == "wide":
+        ix._layer_chunks[cut] = wide_layer_chunks(list(ix.rel_ptr_host)[:R + 2], N, dev)
+    elif cut not in ix._layer_chunks:
+        vptr_host = list(ix.rel_ptr_host) + [P_all + N, P_all + 2 * N]
+        vptr = torch.cat([ix.rel_ptr_dev[:R + 2], torch.tensor([P_all + N, P_all + 2 * N], dtype=I32, device=dev)])
+        ix._layer_chunks[cut] = build_row_tables(vptr, R + 3, P_all + 2 * N, wgrad_chunk_rows(vptr_host, _SMALL_WG), want_ptr=True)
+    jobs = [dict(idx_a=ix.row_in, idx_g=ix.row_out, first_rel=0, row0=0, **conv),
+            dict(colsum_of=1, first_rel=R + 1, row0=P_all, **lin1),
+            dict(colsum_of=1, first_rel=R + 2, row0=P_all + N, **lin2)]
+    gw, cs = rows_wgrad_multi(jobs, ix._layer_chunks[cut], R + 3, H, out_dtype)
+    return (gw[:R], gw[R], cs[R] if has[0] else None, gw[R + 1], cs[R + 1] if has[1] else None, gw[R + 2],
+            cs[R + 2] if has[2] else None)
+
+
 def rgin_layer_wide_ok(x, W, W_loop, bias, linears, index_set):
     """Can a whole RGIN layer run as _RginLayerWideFn?  bf16, H = 256, square, self loop, two square Linears, one index part on the
     closing-launch path (the benchmarked configuration: BASELINE config 5)."""
-    if not (LAYER_WIDE_ENABLED and CHAIN2_ENABLED and W_loop is not None and len(linears) == 2 and len(index_set.parts) == 1):
+    if not (LAYER_WIDE_ENABLED and CHAIN2_ENABLED and W_loop is not None and len(linears) == 2):
         return False
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] == 256 and W.dtype == x.dtype
             and tuple(W.shape[1:]) == (256, 256) and x.shape[0] > 0
             and all(l.weight.dtype == x.dtype and tuple(l.weight.shape) == (256, 256) for l in linears)):
         return False
-    ix = index_set.parts[0][2]
+    ix = index_set.index
     return _selfsum_ok(ix, x) and 0 < ix.num_rows and ix.num_rows + 2 * x.shape[0] <= WIDE_LAYER_MAX_ROWS
 
 
@@ -2562,7 +2581,7 @@ class _RginLayerWideFn(torch.autograd.Function):
     def forward(ctx, x, slope, index_set, W, W_loop, bias, w1, b1, w2, b2):
         ctx.f32_mode = f32_mode()
         x = x.contiguous()
-        ix = index_set.parts[0][2]
+        ix = index_set.index
         pw = PassWeights(W, W_loop, kn=True)
         if not _kn_ok(x):
             pw = pw.nk()
@@ -2578,24 +2597,18 @@ class _RginLayerWideFn(torch.autograd.Function):
     @_backward_in_forward_mode
     def backward(ctx, gout):
         iset, slope = ctx.index_set, ctx.slope
-        ix = iset.parts[0][2]
+        ix = iset.index
         x, h, h1, bits1, bits2, W, W_loop, w1, w2, aux = ctx.saved_tensors
         g = gout.contiguous()
-        N, H, R = x.shape[0], 256, W.shape[0]
+        H, R = 256, W.shape[0]
         g1, g0 = rows_chain2(g, w2, None, False, w1, None, False, mask0_bits=bits2, mask1_bits=bits1, w_kn=(True, True), slope=slope)
         gx = torch.empty_like(x)
         aux_b = message_pass(g0, PassWeights(W, W_loop, kn=False), None, ix, "b", iset.ybuf(H, g.dtype, g.device), gx)
-        # the conv's rows (relation-major, the self loop as relation R), then the two Linears' dense rows, in one virtual row space
-        if getattr(ix, "_layer_chunks", None) is None:
-            ix._layer_chunks = wide_layer_chunks(list(ix.rel_ptr_host)[:R + 2], N, x.device)
-        # (bias gradient = column sum of g0 over the self-loop rows: relation R of the first job)
-        jobs = [dict(A=x, A2=aux if ctx.has[3] else None, idx_a=ix.row_in, G=g0, G2=aux_b, idx_g=ix.row_out,
-                     colsum_of=2 | ((R + 1) << 8), first_rel=0, row0=0),
-                dict(A=g1, G=h, colsum_of=1, first_rel=R + 1, row0=ix.num_rows),
-                dict(A=g, G=h1, colsum_of=1, mask_a_bits=bits2, slope=slope, first_rel=R + 2, row0=ix.num_rows + N)]
-        gw, cs = rows_wgrad_multi(jobs, ix._layer_chunks, R + 3, H, W.dtype)
-        return (gx if ctx.needs_input_grad[0] else None, None, None, gw[:R], gw[R], cs[R] if ctx.has[0] else None, gw[R + 1],
-                cs[R + 1] if ctx.has[1] else None, gw[R + 2], cs[R + 2] if ctx.has[2] else None)
+        # (bias gradient = column sum of g0 over the self-loop rows: relation R of the conv's job)
+        grads = layer_wgrad(ix, "wide", H, W.dtype, ctx.has,
+                            dict(A=x, A2=aux if ctx.has[3] else None, G=g0, G2=aux_b, colsum_of=2 | ((R + 1) << 8)),
+                            dict(A=g1, G=h), dict(A=g, G=h1, mask_a_bits=bits2, slope=slope))
+        return (gx if ctx.needs_input_grad[0] else None, None, None, *grads)
 
 
 def rgin_layer_wide(x, W, W_loop, bias, linears, slope, index_set):
@@ -2611,14 +2624,14 @@ CHAIN2_F32_ENABLED = _os.environ.get("DN_CHAIN2_F32", "1") != "0"          # 0: 
 def rgin_layer_f32_ok(x, W, W_loop, bias, linears, index_set):
     """Can a whole fp32 RGIN layer run as _RginLayerF32Fn?  The reference's precision on the bf16 split (not the exact-f32 mode),
     H = 64 / 128, square, self loop, two square Linears, one part."""
-    if not (LAYER_F32_ENABLED and W_loop is not None and len(linears) == 2 and len(index_set.parts) == 1 and not f32_mode()):
+    if not (LAYER_F32_ENABLED and W_loop is not None and len(linears) == 2 and not f32_mode()):
         return False
     H = x.shape[1] if x.dim() == 2 else 0
     ok = lambda t: t is None or (t.is_cuda and t.dtype == torch.float32)  # noqa: E731
     return (x.is_cuda and x.dtype == torch.float32 and H in (64, 128) and x.shape[0] > 0 and tuple(W.shape[1:]) == (H, H)
             and W.dtype == x.dtype and tuple(W_loop.shape) == (H, H) and ok(W_loop) and ok(bias)
             and all(ok(l.weight) and ok(l.bias) and tuple(l.weight.shape) == (H, H) for l in linears)
-            and index_set.parts[0][2].num_rows > 0 and _kn_ok(x))
+            and index_set.index.num_rows > 0 and _kn_ok(x))
 
 
 class _RginLayerF32Fn(torch.autograd.Function):
@@ -2632,7 +2645,7 @@ class _RginLayerF32Fn(torch.autograd.Function):
     def forward(ctx, x, slope, index_set, W, W_loop, bias, w1, b1, w2, b2, residual=False):
         ctx.f32_mode = f32_mode()
         x = x.contiguous()
-        ix = index_set.parts[0][2]
+        ix = index_set.index
         N, H = x.shape
         slope = float(slope)
         h = torch.empty_like(x)
@@ -2662,36 +2675,27 @@ class _RginLayerF32Fn(torch.autograd.Function):
     @_backward_in_forward_mode
     def backward(ctx, gout):
         iset, slope = ctx.index_set, ctx.slope
-        ix = iset.parts[0][2]
+        ix = iset.index
         x, h, h1, h2, W, W_loop, w1, w2, aux = ctx.saved_tensors
-        N, H, R = x.shape[0], x.shape[1], W.shape[0]
+        N, H = x.shape
         g = gout.contiguous()
         if CHAIN2_F32_ENABLED:
             # outer mask, dgrad 2, inner mask, dgrad 1 in ONE launch; the weight gradient of Linear 2 masks g itself (mask = the saved output)
             gm1, g0 = rows_chain2_f32(g, w2, None, False, w1, None, False, mask0=h2, mask1=h1, w_kn=(True, True), slope=slope)
-            job2 = dict(A=g, G=h1, colsum_of=1, mask_a_bits=h2, slope=slope)
+            job2 = dict(A=g, G=h1, mask_a_bits=h2, slope=slope)
         else:
             tiles, _ = _dense_table(N, x.device)
             gm2 = relu_bwd(g, h2, slope)                                    # the outer activation's mask
             gm1 = rows_transform(gm2, w2.contiguous().unsqueeze(0), tiles, N, mask_pos=h1, slope=slope, w_kn=True)   # masked for the inner one
             g0 = rows_transform(gm1, w1.contiguous().unsqueeze(0), tiles, N, w_kn=True)
-            job2 = dict(A=gm2, G=h1, colsum_of=1)
+            job2 = dict(A=gm2, G=h1)
         gx = torch.empty_like(x)
         # (residual: the gradient of x + layer(x) is g + the layer's input gradient -- g rides in the conv's closing gather)
         aux_b = message_pass(g0, PassWeights(W, W_loop, kn=False), None, ix, "b", iset.ybuf(H, x.dtype, x.device), gx,
                              add_in=g if ctx.residual else None)
-        # the conv's rows (relation-major, the self loop as relation R), then the two Linears' dense rows, in one virtual row space
-        if getattr(ix, "_layer_chunks", None) is None:
-            P_all = ix.num_rows
-            vptr_host = list(ix.rel_ptr_host) + [P_all + N, P_all + 2 * N]
-            vptr = torch.cat([ix.rel_ptr_dev[:R + 2], torch.tensor([P_all + N, P_all + 2 * N], dtype=I32, device=x.device)])
-            ix._layer_chunks = build_row_tables(vptr, R + 3, P_all + 2 * N, wgrad_chunk_rows(vptr_host, _SMALL_WG), want_ptr=True)
-        jobs = [dict(A=x, A2=aux if ctx.has[3] else None, idx_a=ix.row_in, G=g0, G2=aux_b, idx_g=ix.row_out, colsum_of=2, first_rel=0, row0=0),
-                dict(A=gm1, G=h, colsum_of=1, first_rel=R + 1, row0=ix.num_rows),
-                dict(first_rel=R + 2, row0=ix.num_rows + N, **job2)]
-        gw, cs = rows_wgrad_multi(jobs, ix._layer_chunks, R + 3, H, torch.float32)
-        return (gx, None, None, gw[:R], gw[R], cs[R] if ctx.has[0] else None, gw[R + 1], cs[R + 1] if ctx.has[1] else None, gw[R + 2],
-                cs[R + 2] if ctx.has[2] else None, None)
+        grads = layer_wgrad(ix, "small", H, torch.float32, ctx.has, dict(A=x, A2=aux if ctx.has[3] else None, G=g0, G2=aux_b, colsum_of=2),
+                            dict(A=gm1, G=h), job2)
+        return (gx, None, None, *grads, None)
 
 
 def rgin_layer_f32(x, W, W_loop, bias, linears, slope, index_set, residual=False):
@@ -2865,13 +2869,6 @@ def linear_any(x, weight, bias=None, exact=None):
 # ----------------------------------------------------------------------------------------------
 SI_FLAGS = ((1, "a node label outside the label table"), (2, "a node id outside the id table"),
             (4, "a pattern with no nodes"), (8, "a graph with no nodes"), (16, "inconsistent node_ptr"))
-
-
-def launch_tagged(tag, fn):
-    """fn() under kernel_timer's tag when a timer is set (the tags show which SI model path ran)."""
-    if kernel_timer is not None:
-        return kernel_timer.launch(tag, fn)
-    return fn()
 
 
 def _u8_or_none(t):

@@ -374,3 +374,73 @@ def test_wide_rgin_layer_takes_one_weight_gradient_launch(act, graphs):
     _, again = run()
     for a, b in zip(got, again):
         assert torch.equal(a, b)
+
+
+def test_layer_chunk_table_does_not_depend_on_which_layer_touched_the_batch_first():
+    """A graph keeps ONE row index for layers of every width, and the layer functions cache the virtual-row chunk table of their one
+    weight-gradient launch on it: per cut, so that a layer gets the table it would build on a fresh index.  8 dummy-augmented graphs of
+    20 nodes, N = 160 -- between 128 and 256, where the H = 256 cut (the Linears' rows in steps of 128: 128 + 32) and the H = 64 / fp32
+    cut (steps of 256: one chunk) first differ.  The fp32 H = 64 layer after the bf16 H = 256 layer on the same batch: the chunk rows
+    and every gradient bit-equal to the fresh run's; and the other way round the wide layer gets the wide cut."""
+    from dummynode4graphlearning_amd import BatchedGraph, ops
+    from dummynode4graphlearning_amd.subgraph_isomorphism import RGINLayer
+    rng = np.random.default_rng(160)
+    G, R, n = 8, 8, 19
+    src, dst, et, nptr, eptr = [], [], [], [0], [0]
+    for g in range(G):
+        base, m = nptr[-1], 40 + g
+        src += list(base + rng.integers(0, n, size=m)) + list(base + np.arange(n)) + [base + n] * n
+        dst += list(base + rng.integers(0, n, size=m)) + [base + n] * n + list(base + np.arange(n))
+        et += list(rng.integers(0, R - 2, size=m)) + [R - 2] * n + [R - 1] * n
+        nptr.append(base + n + 1); eptr.append(len(src))
+    t = lambda a: torch.tensor(np.asarray(a, dtype=np.int64), device=DEV)  # noqa: E731
+    src, dst, et, N = t(src), t(dst), t(et), nptr[-1]
+    assert N == 160
+    graph = BatchedGraph(src, dst, N, t(np.diff(nptr)), t(np.diff(eptr)), node_ptr=t(nptr), edge_ptr=t(eptr))
+    torch.manual_seed(16)
+    gen = torch.Generator(device=DEV).manual_seed(7)
+    cases = {}
+    for name, H, dtype in (("f32", 64, torch.float32), ("wide", 256, torch.bfloat16)):
+        layer = RGINLayer(H, H, num_rels=R, regularizer="basis", num_bases=-1, num_mlp_layers=2, act_func="relu").to(DEV).to(dtype)
+        cases[name] = (layer, torch.randn(N, H, device=DEV, generator=gen).to(dtype), torch.randn(N, H, device=DEV, generator=gen).to(dtype))
+
+    def run(name):
+        """-> (the non-empty rows of the chunk table the layer's weight-gradient launch took, [out, x.grad, parameter gradients])"""
+        layer, x0, coef = cases[name]
+        for p in layer.parameters():
+            p.grad = None
+        x = x0.clone().requires_grad_(True)
+        seen, inner = [], ops.rows_wgrad_multi
+
+        def recording(jobs, chunk_table, *a, **kw):
+            seen.append(chunk_table[0])
+            return inner(jobs, chunk_table, *a, **kw)
+        ops.rows_wgrad_multi = recording
+        try:
+            out, _ = layer(graph, x, et)
+            out.backward(coef)
+        finally:
+            ops.rows_wgrad_multi = inner
+        assert len(seen) == 1, name                                          # the layer function with ONE weight-gradient launch ran
+        rows = seen[0][seen[0][:, 2] > seen[0][:, 1]].clone()
+        return rows, [out.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in layer.parameters() if p.grad is not None]
+
+    def linears_rows(rows):
+        return (rows[rows[:, 0] > R][:, 2] - rows[rows[:, 0] > R][:, 1]).tolist()
+
+    rows_f32, grads_f32 = run("f32")                                         # fresh index
+    assert linears_rows(rows_f32) == [160, 160]
+    graph._cache.clear()
+    rows_wide, grads_wide = run("wide")                                      # fresh index
+    assert linears_rows(rows_wide) == [128, 32, 128, 32]
+    ix = graph.row_index(et, R, True).parts[0][2]
+    want = ops.wide_layer_chunks(list(ix.rel_ptr_host), N, DEV)
+    assert torch.equal(rows_wide, want[0][:want[2]])
+    rows, grads = run("f32")                                                 # ... the index the wide layer has used
+    assert torch.equal(rows, rows_f32), (rows.tolist(), rows_f32.tolist())
+    assert len(grads) == len(grads_f32) and all(torch.equal(a, b) for a, b in zip(grads, grads_f32))
+    graph._cache.clear()
+    run("f32")
+    rows, grads = run("wide")                                                # ... and the other way round
+    assert torch.equal(rows, rows_wide), (rows.tolist(), rows_wide.tolist())
+    assert len(grads) == len(grads_wide) and all(torch.equal(a, b) for a, b in zip(grads, grads_wide))
