@@ -5,5 +5,6 @@ built library or with CPU tensors."""
 from . import graph, ops, transforms, tu_io  # noqa: F401
 from .graph import BatchedGraph, GraphBatch  # noqa: F401
 from .hipgraph import StepGraph  # noqa: F401
+from .loader import BatchLoader, PackedGraphs  # noqa: F401
 
 __version__ = "0.1.0"

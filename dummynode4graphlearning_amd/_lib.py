@@ -23,6 +23,12 @@ class WgradJob(ctypes.Structure):
                 ("colsum_of", c_i32), ("first_rel", c_i32), ("row0", c_i32), ("act_slope", c_f32)]
 
 
+class BatchCol(ctypes.Structure):
+    """dn_batch_col of include/dn_hip.h (one column of a dn_batch_assemble launch)."""
+    _fields_ = [("src", P), ("dst", P), ("row_bytes", c_i32), ("level", c_i32), ("rebase", c_i32), ("int_width", c_i32),
+                ("src_global", c_i32), ("ptr_tail", c_i32)]
+
+
 # name -> (restype, argtypes); mirrors include/dn_hip.h one to one
 _SIGS = {
     "dn_version": (ctypes.c_int, []),
@@ -153,6 +159,7 @@ _SIGS = {
                                            c_i32, P, P, P]),
     "dn_sie_pool_sum_bf16": (ctypes.c_int, [c_i64, P, P, P, P, c_i64, P, P, c_i32, c_i32, P, P, c_i32, c_i32, P, P, c_i32, c_i32, P, P, P,
                                             c_i32, P, P, P]),
+    "dn_batch_assemble": (ctypes.c_int, [c_i64, P, P, P, c_i64, c_i64, c_i64, ctypes.POINTER(BatchCol), c_i32, P, P]),
 }
 
 _lib = None

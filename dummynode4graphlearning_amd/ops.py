@@ -862,6 +862,28 @@ class EdgeIndex:
         self.bwd = _SplitCSR(self.out_ptr, self.dst_by_src, num_nodes)
         self._max_bwd = None
 
+    @classmethod
+    def from_parts(cls, src, dst, num_nodes, node_ptr, in_ptr, in_perm, src_by_dst, out_ptr, out_perm, dst_by_src):
+        """The index of a batch whose CSR by destination / CSC by source already exist (loader.PackedGraphs.assemble copies them out
+        of the dataset's own, re-based): the six tensors are taken as they are -- int32, what __init__ would have built from
+        (src, dst) -- and the hub split and the tile plan are derived from them exactly as there."""
+        require_gpu(src, dst, in_ptr, in_perm, src_by_dst, out_ptr, out_perm, dst_by_src)
+        self = cls.__new__(cls)
+        self.num_nodes, self.num_edges = int(num_nodes), int(src.numel())
+        for name, t, n in (("in_ptr", in_ptr, self.num_nodes + 1), ("out_ptr", out_ptr, self.num_nodes + 1), ("in_perm", in_perm, self.num_edges),
+                           ("out_perm", out_perm, self.num_edges), ("src_by_dst", src_by_dst, self.num_edges),
+                           ("dst_by_src", dst_by_src, self.num_edges)):
+            if _i32(t, name).numel() != n:
+                raise _lib.DnHipError("%s has %d entries, expected %d" % (name, t.numel(), n))
+        self._node_ptr, self._plan = node_ptr, None
+        self.src, self.dst = src.to(I32).contiguous(), dst.to(I32).contiguous()
+        self.in_ptr, self.in_perm, self.out_ptr, self.out_perm = in_ptr, in_perm, out_ptr, out_perm
+        self.src_by_dst, self.dst_by_src = src_by_dst, dst_by_src
+        self.fwd = _SplitCSR(self.in_ptr, self.src_by_dst, self.num_nodes)
+        self.bwd = _SplitCSR(self.out_ptr, self.dst_by_src, self.num_nodes)
+        self._max_bwd = None
+        return self
+
     def tile_plan(self):
         """Plan of the matrix-core neighbour sum (dn_graph_tile_sum_f32) for this batch, or None: tiles = greedy runs of whole
         graphs with at most 64 rows (packed by dn_graph_tiles_host from one small copy of the graph boundaries), the rows of larger

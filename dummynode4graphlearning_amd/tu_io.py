@@ -368,5 +368,10 @@ class PYGDataset:
         """GraphBatch of the given graphs (what DataLoader(dataset, batch_size) yields, main.py:245-247)."""
         return GraphBatch.collate([self[int(i)] for i in indices])
 
+    def packed(self):
+        """loader.PackedGraphs over this dataset's tensors (no copy): packed().assemble(indices) == batch(indices) in one launch."""
+        from .loader import PackedGraphs
+        return PackedGraphs.from_pyg_dataset(self)
+
     def __repr__(self):
         return "%s(%d)" % (self.name, len(self))

@@ -908,6 +908,42 @@ int dn_sie_pool_sum_bf16(int64_t B, const int32_t* edge_ptr, const uint8_t* skip
                          int32_t rows_el, int32_t Kel, const int32_t* out_deg, const int32_t* in_deg, const void* rep, int32_t H,
                          float* pooled, int32_t* count, dn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mini-batch assembly from a device-resident dataset: ONE launch builds a batch's tensors from the packed dataset's columns
+ * (a batched ragged copy with optional integer re-basing).
+ * Replaces: the host-side collate of every training step -- DataLoader + torch_geometric Batch.from_data_list
+ *   (graph_classification/graph_neural_networks/main.py:245-247) and batchify -> dgl.batch
+ *   (subgraph_isomorphism/dataset.py:1321-1328, 1605-1611).
+ * The dataset keeps, per column, the rows of graph i in [ds_ptr[i], ds_ptr[i+1]) -- ds_node_ptr for node-level columns,
+ * ds_edge_ptr for edge-level ones, row i for graph-level ones; num_ds_graphs = the number of graphs behind those arrays.
+ * table = {ids [B], out_node_ptr [B+1], out_edge_ptr [B+1]} int32, one device array: output graph k = dataset graph ids[k]
+ * (any order, duplicates allowed), its rows go to [out_ptr[k], out_ptr[k+1]) of every column; N = out_node_ptr[B],
+ * E = out_edge_ptr[B] (the caller planned them on the host).  A graph whose id is outside [0, num_ds_graphs) or whose planned
+ * size differs from the dataset's is skipped, never read.
+ * Column c copies row_bytes (>= 1, any value) bytes per row from src to dst; the two sides may be aligned differently.
+ * rebase != DN_BATCH_REBASE_NONE: the rows are integers of int_width (4 or 8) bytes, row_bytes a multiple of it, src and dst
+ * aligned to it, and every value v is written as  v - base_in + base_out:  base_out = out_node_ptr[k] (REBASE_NODE) or
+ * out_edge_ptr[k] (REBASE_EDGE); base_in = 0 when the dataset stores graph-local values (src_global == 0: the endpoints of an
+ * edge list), ds_node_ptr[i] / ds_edge_ptr[i] when it stores dataset-global ones (src_global != 0: a CSR built over the whole
+ * dataset).  ptr_tail != 0 (re-based columns only): one more value behind the column's last row, = N or E by `rebase` (the closing
+ * entry of a CSR pointer array).  batch_out (may be NULL) [N] int64: k for every node of output graph k (the PyG `batch` vector).
+ * num_cols <= DN_BATCH_MAX_COLS.  No atomics, no workspace; B == 0 or nothing to write: returns 0 without a launch. */
+#define DN_BATCH_MAX_COLS 32
+#define DN_BATCH_LEVEL_NODE 0
+#define DN_BATCH_LEVEL_EDGE 1
+#define DN_BATCH_LEVEL_GRAPH 2
+#define DN_BATCH_REBASE_NONE 0
+#define DN_BATCH_REBASE_NODE 1
+#define DN_BATCH_REBASE_EDGE 2
+typedef struct dn_batch_col {
+    const void* src;
+    void* dst;
+    int32_t row_bytes, level, rebase, int_width, src_global, ptr_tail;
+} dn_batch_col;
+int dn_batch_assemble(int64_t B, const int32_t* table, const int32_t* ds_node_ptr, const int32_t* ds_edge_ptr,
+                      int64_t num_ds_graphs, int64_t N, int64_t E, const dn_batch_col* host_cols, int32_t num_cols,
+                      int64_t* batch_out, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
