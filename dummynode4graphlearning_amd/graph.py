@@ -22,10 +22,12 @@ class _IndexCache:
     def __init__(self):
         self._edge_index = None
         self._rel = []  # [(etype tensor, version, num_rels, RelIndex)]
+        self._lrp = {}  # {sequence length: ops.LrpIndex}
 
     def clear(self):
         self._edge_index = None
         self._rel = []
+        self._lrp = {}
 
 
 class BatchedGraph:
@@ -141,6 +143,15 @@ class BatchedGraph:
         self._cache._rel.append((etype, etype._version, ("row", num_rels, self_loop), ix))
         if len(self._cache._rel) > 4:
             self._cache._rel.pop(0)
+        return ix
+
+    def lrp_index(self, seq_len):
+        """Cached ops.LrpIndex (ego-net index of the LRP model): the edges with is_reversed == 0, the nodes' is_dummy flags."""
+        ix = self._cache._lrp.get(int(seq_len))
+        if ix is None:
+            ix = ops.LrpIndex(self._src, self._dst, self._n, seq_len, rev=self.edata.get("is_reversed"),
+                              dummy=self.ndata.get("is_dummy"), node_ptr=self.node_ptr())
+            self._cache._lrp[int(seq_len)] = ix
         return ix
 
     # ---- dgl.batch (dataset.py:1321-1328, 1609-1610) ----------------------------------------------

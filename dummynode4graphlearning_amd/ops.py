@@ -3416,3 +3416,282 @@ def sie_pool_sum(rep, edge_ptr, skip=None, src=None, dst=None, id_=None, enc_v=N
     return _SiePoolSumFn.apply(rep, edge_ptr, _u8_or_none(skip), src, dst, id_, enc_v.contiguous() if enc_v is not None else None,
                                vlabel, enc_vl.contiguous() if enc_vl is not None else None, elabel,
                                enc_el.contiguous() if enc_el is not None else None, out_deg, in_deg)
+
+
+# ----------------------------------------------------------------------------------------------
+# LRP (local relational pooling) of the SI count model LRP: ego-net index and pooling (dn_lrp.hip)
+# ----------------------------------------------------------------------------------------------
+LRP_SEQ_LENS = (2, 3, 4)
+LRP_MAX_H = 256
+LRP_LEAKY_SLOPE = 1.0 / 5.5              # the reference's leaky_relu (subgraph_isomorphism/utils/act.py)
+# LDS budget of dn_lrp_pool_*: an ego of d + 1 nodes keeps its T_node rows in LDS while (d + 1) * L * H * 4 <= LRP_STAGE_BYTES and
+# its pair -> edge table while d + 1 <= LRP_PAIR_NODES (checked against the library when the first index is built)
+LRP_STAGE_BYTES = 56 * 1024
+LRP_PAIR_NODES = 64
+# The default path of ops.lrp_pool.  Measured on the config-3 scale batch (docs/LAB_NOTES.md "LRP"): with one workgroup per node the
+# fused kernels lose to the composed path when every ego is small (LRPLayer step 4.5 ms against 2.9 ms at L = 4), so the composed
+# path is the default and the fused kernels are an opt-in (`with ops.lrp_fused():`) -- and the path of a batch whose sequence
+# list does not fit the materialised index (hub egos), where the composed path cannot run at all.
+LRP_FUSED_DEFAULT = False
+_lrp_tls = _threading.local()
+_INT32_MAX = 2 ** 31 - 1
+
+
+def lrp_stage_nodes(H, seq_len):
+    """Largest ego (the node and its neighbours) whose table rows dn_lrp_pool_* stages in LDS at width H."""
+    return LRP_STAGE_BYTES // (int(seq_len) * int(H) * 4)
+
+
+def lrp_fused_enabled():
+    m = getattr(_lrp_tls, "fused", None)
+    return LRP_FUSED_DEFAULT if m is None else m
+
+
+class lrp_fused:
+    """Context manager: ops.lrp_pool calls started inside it (on this thread) run on dn_lrp_pool_* where the width allows it."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_lrp_tls, "fused", None)
+        _lrp_tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _lrp_tls.fused = self.old
+        return False
+
+
+class lrp_composed(lrp_fused):
+    """Context manager: force the composed path (gather_segsum over the materialised index + dn_segment_mean / _sum), whatever
+    the default -- the A/B partner of the fused kernels and the path of widths they do not take."""
+
+    def __init__(self, on=True):
+        super().__init__(not on)
+
+
+def lrp_fused_supported(H):
+    return 16 <= int(H) <= LRP_MAX_H and int(H) % 16 == 0
+
+
+class LrpPermIndex(NamedTuple):
+    perm_ptr: torch.Tensor       # [N + 1] int32
+    perm_nodes: torch.Tensor     # [P, L] int32, -1 = empty
+    perm_edges: torch.Tensor     # [P, L * L] int32, -1 = empty
+
+
+class LrpIndex:
+    """Ego-net index of a batch for sequence length L (dn_lrp.hip): the sorted duplicate-free out-neighbour lists over the edges
+    with is_reversed == 0 (uptr / unbr, with ueid = the last edge id of every pair), per node its kind, its dummy neighbours, the
+    neighbour positions split into non-dummy / dummy (upos) and its sequence count (int64).  Nothing here is sized by the number
+    of sequences; the one device-to-host read is the error word (a self-loop among the counted edges raises DnHipError)."""
+
+    def __init__(self, src, dst, num_nodes, seq_len, rev=None, dummy=None, node_ptr=None):
+        if int(seq_len) not in LRP_SEQ_LENS:
+            raise ValueError("lrp_seq_len must be one of %s (got %s)" % (LRP_SEQ_LENS, seq_len))
+        require_gpu(src, dst, rev, dummy)
+        if lib().dn_lrp_stage_bytes() != LRP_STAGE_BYTES or lib().dn_lrp_pair_nodes() != LRP_PAIR_NODES:
+            raise _lib.DnHipError("ops.LRP_STAGE_BYTES / LRP_PAIR_NODES differ from the library's")
+        N, E, dev = int(num_nodes), int(src.numel()), src.device
+        self.num_nodes, self.num_edges, self.seq_len = N, E, int(seq_len)
+        big = N * N
+        key = src.long() * N + dst.long()
+        if rev is not None:
+            key = torch.where(rev.reshape(-1).bool(), torch.full_like(key, big), key)
+        ks, order = torch.sort(key, stable=True)
+        # the last entry of every run of equal keys: the pair's largest edge id (stable sort); everything else lands in slot E
+        last = (ks < big) & (ks != torch.cat([ks[1:], ks.new_full((1,), -1)]))
+        tgt = torch.where(last, torch.cumsum(last, 0) - 1, torch.full_like(ks, E))
+        self.unbr = torch.zeros(E + 1, dtype=I32, device=dev).scatter_(0, tgt, (ks % N).to(I32))
+        self.ueid = torch.zeros(E + 1, dtype=I32, device=dev).scatter_(0, tgt, order.to(I32))
+        deg = torch.zeros(N + 1, dtype=torch.long, device=dev).scatter_add_(
+            0, torch.where(last, ks // max(N, 1), torch.full_like(ks, N)), torch.ones_like(ks))
+        self.uptr = torch.cat([deg.new_zeros(1), torch.cumsum(deg[:N], 0)]).to(I32)
+        self.upos = torch.zeros(E + 1, dtype=I32, device=dev)
+        self.ego = torch.zeros((N, 2), dtype=I32, device=dev)
+        self.count = torch.ones(N, dtype=torch.long, device=dev)
+        self.dummy = _u8_or_none(dummy)
+        err = torch.tensor([_INT32_MAX, 0], dtype=I32, device=dev)
+        check(lib().dn_lrp_ego_index_i32(N, self.seq_len, ptr(self.uptr), ptr(self.unbr), ptr(self.dummy), ptr(self.upos),
+                                         ptr(self.ego), ptr(self.count), ptr(err), stream_ptr()), "dn_lrp_ego_index_i32")
+        loop, flags = err.tolist()
+        if loop != _INT32_MAX:
+            where = ""
+            if node_ptr is not None:
+                g = int(torch.searchsorted(node_ptr.long(), torch.tensor([loop], device=node_ptr.device), right=True)) - 1
+                where = " (node %d of graph %d)" % (loop - int(node_ptr[g]), g)
+            raise _lib.DnHipError("LRP index: a self-loop on batch node %d%s; the ego-net sequences are undefined for it" % (loop, where))
+        if flags & 1:
+            raise _lib.DnHipError("LRP index: a node's sequence count does not fit 64 bits")
+        self._perm = None
+        self._composed = None
+        self._total = None
+
+    def _args(self):
+        return (ptr(self.uptr), ptr(self.unbr), ptr(self.ueid), ptr(self.upos), ptr(self.ego), ptr(self.count))
+
+    def num_sequences(self):
+        """P, the batch's sequence total (one device-to-host read, kept)."""
+        if self._total is None:
+            self._total = int(self.count.sum())
+        return self._total
+
+    def materialisable(self):
+        return self.num_sequences() * self.seq_len * self.seq_len <= _INT32_MAX
+
+    def perm_index(self):
+        """The materialised index (LrpPermIndex), built by count -> scan -> fill and kept; reads the sequence total back once."""
+        if self._perm is None:
+            N, L = self.num_nodes, self.seq_len
+            P = self.num_sequences()
+            ptr64 = torch.cat([self.count.new_zeros(1), torch.cumsum(self.count, 0)])
+            if not self.materialisable():
+                raise _lib.DnHipError("LRP index: %d sequences do not fit an int32 index; use the fused path" % P)
+            perm_ptr = ptr64.to(I32)
+            nodes = torch.empty((P, L), dtype=I32, device=perm_ptr.device)
+            edges = torch.empty((P, L * L), dtype=I32, device=perm_ptr.device)
+            check(lib().dn_lrp_perm_fill_i32(N, L, *self._args(), ptr(perm_ptr), P, ptr(nodes), ptr(edges), stream_ptr()),
+                  "dn_lrp_perm_fill_i32")
+            self._perm = LrpPermIndex(perm_ptr, nodes, edges)
+        return self._perm
+
+    def composed_tables(self):
+        """(idx, ptr, csr of idx, segment of every entry) of the composed path over the stacked table [N L + E L (L - 1), H]:
+        sequence p gathers row node * L + k for its k-th node and row N L + eid * L (L - 1) + slot for every edge it holds."""
+        if self._composed is None:
+            pi = self.perm_index()
+            N, E, L = self.num_nodes, self.num_edges, self.seq_len
+            P, dev = pi.perm_nodes.shape[0], pi.perm_nodes.device
+            k = torch.arange(L, device=dev)
+            slot = torch.arange(L * L, device=dev)
+            a, b = slot // L, slot % L
+            off = a * (L - 1) + torch.where(b > a, b - 1, b)
+            rows = torch.full((P, L + L * L), -1, dtype=torch.long, device=dev)
+            rows[:, :L] = torch.where(pi.perm_nodes >= 0, pi.perm_nodes.long() * L + k, rows[:, :L])
+            rows[:, L:] = torch.where(pi.perm_edges >= 0, N * L + pi.perm_edges.long() * (L * (L - 1)) + off, rows[:, L:])
+            keep = rows >= 0
+            idx = rows[keep].to(I32).contiguous()
+            ptr_ = torch.cat([keep.new_zeros(1, dtype=torch.long), torch.cumsum(keep.sum(1), 0)]).to(I32)
+            seg = torch.repeat_interleave(torch.arange(P, device=dev, dtype=I32), keep.sum(1), output_size=idx.numel())
+            tptr, tperm = csr_build(idx, N * L + E * L * (L - 1))
+            self._composed = (idx, ptr_, tptr, seg.index_select(0, tperm.long()).contiguous())
+        return self._composed
+
+
+def _lrp_index_of(graph, seq_len):
+    if isinstance(graph, LrpIndex):
+        if graph.seq_len != int(seq_len):
+            raise ValueError("the LRP index was built for sequence length %d, not %d" % (graph.seq_len, seq_len))
+        return graph
+    return graph.lrp_index(seq_len)
+
+
+def lrp_perm_index(graph, seq_len=4):
+    """The materialised ego-net permutation index of a BatchedGraph (or an LrpIndex): LrpPermIndex(perm_ptr [N + 1],
+    perm_nodes [P, L], perm_edges [P, L * L]), int32 with -1 for empty; as row / column lists it is the reference's
+    node_to_perm / edge_to_perm matrices (dataset.py:1843-1886), order included."""
+    return _lrp_index_of(graph, seq_len).perm_index()
+
+
+class _GatherSegsumFn(torch.autograd.Function):
+    """out[s] = sum of x[idx[i]] over segment s (gather_segsum); backward: the same kernel over the transposed lists."""
+
+    @staticmethod
+    def forward(ctx, x, idx, ptr_, tptr, tseg):
+        ctx.tables, ctx.rows = (tptr, tseg), x.shape[0]
+        return gather_segsum(x.contiguous(), idx, ptr_)
+
+    @staticmethod
+    def backward(ctx, g):
+        tptr, tseg = ctx.tables
+        return gather_segsum(g.contiguous(), tseg, tptr, ctx.rows), None, None, None, None
+
+
+class _LrpPoolFn(torch.autograd.Function):
+    """The fused pooling (dn_lrp_pool_fwd_f32 / _bwd_f32) over the row-factorised tables t_node [N, L H], t_edge [E, L (L-1) H].
+    The backward adds into zeroed tables with fp32 atomics: exact sums, not bit-repeatable on general inputs."""
+
+    @staticmethod
+    def forward(ctx, t_node, t_edge, bias, factor, ix, H, pool_mean, act_on, slope):
+        t_node, t_edge = t_node.contiguous(), t_edge.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        factor = None if factor is None else factor.contiguous()
+        require_gpu(t_node, t_edge, bias, factor)
+        N, E, L = ix.num_nodes, ix.num_edges, ix.seq_len
+        if t_node.shape != (N, L * H) or t_edge.shape != (E, L * (L - 1) * H) or t_node.dtype != torch.float32 or \
+                t_edge.dtype != torch.float32 or (factor is not None and (factor.shape != (N, H) or factor.dtype != torch.float32)) or \
+                (bias is not None and (bias.numel() != H or bias.dtype != torch.float32)):
+            raise _lib.DnHipError("lrp_pool: fp32 t_node [N, L H], t_edge [E, L (L - 1) H], bias [H], factor [N, H] expected")
+        out = torch.empty((N, H), dtype=torch.float32, device=t_node.device)
+        pooled = torch.empty_like(out) if factor is not None else None
+        launch_tagged("lrp_pool_fwd", lambda: check(lib().dn_lrp_pool_fwd_f32(
+            N, E, H, L, *ix._args(), ptr(t_node), ptr(t_edge), ptr(bias), ptr(factor), int(pool_mean), int(act_on), float(slope),
+            ptr(pooled), ptr(out), stream_ptr()), "dn_lrp_pool_fwd_f32"))
+        ctx.ix, ctx.H, ctx.mode = ix, H, (int(pool_mean), int(act_on), float(slope))
+        ctx.has = (bias is not None, factor is not None)
+        empty = t_node.new_empty(0)
+        ctx.save_for_backward(t_node, t_edge, bias if bias is not None else empty, factor if factor is not None else empty,
+                              pooled if pooled is not None else empty)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        t_node, t_edge, bias, factor, pooled = ctx.saved_tensors
+        ix, H = ctx.ix, ctx.H
+        has_bias, has_factor = ctx.has
+        g = g.contiguous().float()
+        d_tnode, d_tedge = torch.zeros_like(t_node), torch.zeros_like(t_edge)
+        d_bias = torch.zeros(H, dtype=torch.float32, device=g.device) if has_bias else None
+        d_factor = torch.empty_like(g) if has_factor else None
+        launch_tagged("lrp_pool_bwd", lambda: check(lib().dn_lrp_pool_bwd_f32(
+            ix.num_nodes, ix.num_edges, H, ix.seq_len, *ix._args(), ptr(t_node), ptr(t_edge), ptr(bias) if has_bias else None,
+            ptr(factor) if has_factor else None, *ctx.mode, ptr(pooled) if has_factor else None, ptr(g), ptr(d_tnode), ptr(d_tedge),
+            ptr(d_bias), ptr(d_factor), stream_ptr()), "dn_lrp_pool_bwd_f32"))
+        return d_tnode, d_tedge, d_bias, d_factor, None, None, None, None, None
+
+
+def _lrp_act(t, act):
+    if act == "relu":
+        return torch.relu(t)
+    if act == "leaky_relu":
+        return torch.nn.functional.leaky_relu(t, LRP_LEAKY_SLOPE)
+    return t
+
+
+def lrp_pool(x, edge_feat, weight, bias, factor, graph, seq_len=4, act="relu", pool="mean"):
+    """[N, H] = act(pool_p(act(sum_slots W_slot^T row_slot + bias)) * factor) of lrp.py:65-75 without its [P L^2, in] tensor.
+    x [N, in], edge_feat [E, in], weight [in, H, L^2] (the reference's parameter), bias [H] or None, factor [N, H] or None (then no
+    scale and no second activation), graph a BatchedGraph (its cached LrpIndex) or an LrpIndex; act "relu" | "leaky_relu"
+    (slope 1 / 5.5) | "none"; pool "mean" | "sum".  fp32.  The weight is row-factorised: T_node = x @ [W_0 | W_(L+1) | ...] and
+    T_edge = edge_feat @ [off-diagonal slots] on the Linear kernels (linear_any), then dn_lrp_pool_* (one workgroup per node
+    enumerates the node's sequences; `with ops.lrp_fused():`, and by itself when the sequence list does not fit the materialised
+    index) -- or, by default and for widths the kernel does not take, gather_segsum over the materialised index and
+    dn_segment_mean / _sum (ops.LRP_FUSED_DEFAULT)."""
+    if act not in ("relu", "leaky_relu", "none") or pool not in ("mean", "sum"):
+        raise ValueError("lrp_pool: act in relu | leaky_relu | none and pool in mean | sum (got %s, %s)" % (act, pool))
+    ix = _lrp_index_of(graph, seq_len)
+    L = ix.seq_len
+    if weight.dim() != 3 or weight.shape[2] != L * L or x.shape[1] != weight.shape[0] or edge_feat.shape[1] != weight.shape[0]:
+        raise _lib.DnHipError("lrp_pool: weight [in, H, L * L] with in = the width of x and edge_feat expected")
+    if x.shape[0] != ix.num_nodes or edge_feat.shape[0] != ix.num_edges:
+        raise _lib.DnHipError("lrp_pool: one x row per node and one edge_feat row per edge of the indexed batch expected")
+    require_gpu(x.contiguous(), edge_feat.contiguous())
+    H = int(weight.shape[1])
+    wt = weight.permute(2, 1, 0)                                          # [L * L, H, in]
+    diag = [k * (L + 1) for k in range(L)]
+    off = [s for s in range(L * L) if s % (L + 1) != 0]
+    t_node = linear_any(x, wt[diag].reshape(L * H, -1))                   # [N, L * H]
+    t_edge = linear_any(edge_feat, wt[off].reshape(L * (L - 1) * H, -1))  # [E, L * (L - 1) * H]
+    forced = getattr(_lrp_tls, "fused", None)
+    fused = (LRP_FUSED_DEFAULT or not ix.materialisable()) if forced is None else forced
+    if fused and lrp_fused_supported(H) and x.dtype == torch.float32:
+        slope = LRP_LEAKY_SLOPE if act == "leaky_relu" else 0.0
+        return _LrpPoolFn.apply(t_node, t_edge, bias, factor, ix, H, pool == "mean", act != "none", slope)
+    idx, ptr_, tptr, tseg = ix.composed_tables()
+    table = torch.cat([t_node.reshape(-1, H), t_edge.reshape(-1, H)], 0)
+    z = _GatherSegsumFn.apply(table, idx, ptr_, tptr, tseg)
+    if bias is not None:
+        z = z + bias
+    out = segment_reduce(_lrp_act(z, act), ix.perm_index().perm_ptr, pool)
+    return out if factor is None else _lrp_act(out * factor, act)

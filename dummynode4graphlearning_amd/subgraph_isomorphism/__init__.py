@@ -7,3 +7,4 @@ from .dl import split_and_batchify_graph_feats  # noqa: F401
 from .graph_adj import (EquivariantEmbedding, GraphAdjModel, MultihotEmbedding, NormalEmbedding, OrthogonalEmbedding,  # noqa: F401
                         OutputDict, PositionEmbedding, RGCN, RGIN, ScalarFilter, UniformEmbedding)
 from .graph_adj_v2 import CompGCN, DMPNN, GraphAdjModelV2  # noqa: F401
+from .lrp import LRP, LRPLayer  # noqa: F401

@@ -944,6 +944,45 @@ int dn_batch_assemble(int64_t B, const int32_t* table, const int32_t* ds_node_pt
                       int64_t num_ds_graphs, int64_t N, int64_t E, const dn_batch_col* host_cols, int32_t num_cols,
                       int64_t* batch_out, dn_stream_t stream);
 
+/* ---- LRP (local relational pooling) of the SI count model LRP: ego-net permutation index and pooling (dn_lrp.hip) ----
+ * The ego index of a batch: uptr [N + 1] / unbr / ueid = the sorted, duplicate-free out-neighbour lists over the edges that count
+ * (is_reversed == 0) with the LAST edge id of every (u, w) -- built by the caller -- and, from dn_lrp_ego_index_i32:
+ *     upos  [uptr[N]]  per node the positions (into its neighbour list) of its non-dummy neighbours, then of its dummy neighbours
+ *     ego   [N, 2]     {kind, dummy neighbours}: kind 0 = permutations of the neighbours, 1 = the node is a dummy (combinations),
+ *                      2 = the node has dummy neighbours (permutations of the others, one dummy neighbour last)
+ *     count [N] int64  sequences of the node for sequence length L (2, 3 or 4); saturates at INT64_MAX
+ *     err   [2]        caller-initialised {INT32_MAX, 0}: [0] = the smallest node with a self-loop, [1] bit 0 = a count saturated
+ * dummy (uint8 [N]) may be NULL.  N == 0: returns 0 without a launch (as every entry point below). */
+int dn_lrp_ego_index_i32(int64_t N, int32_t L, const int32_t* uptr, const int32_t* unbr, const uint8_t* dummy, int32_t* upos,
+                         int32_t* ego, int64_t* count, int32_t* err, dn_stream_t stream);
+/* The materialised index: perm_nodes [P, L] and perm_edges [P, L * L] (-1 = empty) for perm_ptr [N + 1] = the exclusive scan of
+ * count; sequence p of node v fills slot k (L + 1) with its k-th node and slot a L + b with eid(node a, node b) where that edge
+ * exists.  Order: the reference's (subgraph_isomorphism/dataset.py:1750-1823).  P * L * L must fit int32. */
+int dn_lrp_perm_fill_i32(int64_t N, int32_t L, const int32_t* uptr, const int32_t* unbr, const int32_t* ueid, const int32_t* upos,
+                         const int32_t* ego, const int64_t* count, const int32_t* perm_ptr, int64_t P, int32_t* perm_nodes,
+                         int32_t* perm_edges, dn_stream_t stream);
+/* LDS budget of the pooling kernels: an ego of d + 1 nodes keeps its T_node rows in LDS when (d + 1) L H 4 <= dn_lrp_stage_bytes()
+ * and its pair -> edge table when d + 1 <= dn_lrp_pair_nodes(); larger egos read through L2. */
+int32_t dn_lrp_stage_bytes(void);
+int32_t dn_lrp_pair_nodes(void);
+/* out [N, H] = act2(pool_p(act(sum_k t_node[node_k(p)][k] + sum_(a != b) t_edge[eid_ab(p)][slot(a, b)] + bias)) * factor), one
+ * workgroup per node, the sequences enumerated in the kernel from the ego index; nothing of size P is stored.
+ * t_node [N, L, H] (x times the diagonal slots of the weight), t_edge [E, L (L - 1), H] (edge features times the off-diagonal
+ * slots, in slot order); bias [H] and factor [N, H] may be NULL (no factor: no scale and no second activation); pool_mean: mean
+ * instead of sum; act_on: leaky ReLU of `slope` (0: ReLU), else the identity.  pooled [N, H] (may be NULL) receives the pooled
+ * value in front of the factor (the backward needs it when factor is given).  H a multiple of 16, 16 <= H <= 256. */
+int dn_lrp_pool_fwd_f32(int64_t N, int64_t E, int32_t H, int32_t L, const int32_t* uptr, const int32_t* unbr, const int32_t* ueid,
+                        const int32_t* upos, const int32_t* ego, const int64_t* count, const float* t_node, const float* t_edge,
+                        const float* bias, const float* factor, int32_t pool_mean, int32_t act_on, float slope, float* pooled,
+                        float* out, dn_stream_t stream);
+/* Backward: recomputes every sequence and ADDS its gradient rows into d_tnode [N, L, H], d_tedge [E, L (L - 1), H] and d_bias [H]
+ * (may be NULL) with fp32 atomics -- the caller zeroes them; sums across egos are exact but their order is not fixed.  d_factor
+ * [N, H] is stored (needs factor and pooled). */
+int dn_lrp_pool_bwd_f32(int64_t N, int64_t E, int32_t H, int32_t L, const int32_t* uptr, const int32_t* unbr, const int32_t* ueid,
+                        const int32_t* upos, const int32_t* ego, const int64_t* count, const float* t_node, const float* t_edge,
+                        const float* bias, const float* factor, int32_t pool_mean, int32_t act_on, float slope, const float* pooled,
+                        const float* g, float* d_tnode, float* d_tedge, float* d_bias, float* d_factor, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
