@@ -162,6 +162,8 @@ _SIGS = {
     "dn_batch_assemble": (ctypes.c_int, [c_i64, P, P, P, c_i64, c_i64, c_i64, ctypes.POINTER(BatchCol), c_i32, P, P]),
     "dn_lrp_ego_index_i32": (ctypes.c_int, [c_i64, c_i32] + [P] * 7 + [P]),
     "dn_lrp_perm_fill_i32": (ctypes.c_int, [c_i64, c_i32] + [P] * 7 + [c_i64, P, P, P]),
+    "dn_lrp_collapse_count_i32": (ctypes.c_int, [c_i64, c_i64, c_i32] + [P] * 8 + [P]),
+    "dn_lrp_collapse_fill_i32": (ctypes.c_int, [c_i64, c_i64, c_i32] + [P] * 8 + [c_i64, P, P, P]),
     "dn_lrp_stage_bytes": (c_i32, []),
     "dn_lrp_pair_nodes": (c_i32, []),
     "dn_lrp_pool_fwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32] + [P] * 10 + [c_i32, c_i32, c_f32, P, P, P]),

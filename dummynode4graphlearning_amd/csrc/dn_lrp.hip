@@ -5,6 +5,8 @@
 // a third sparse product that pools the P sequences per node).  Here the einsum is row-factorised (T_node = x @ diagonal slots,
 // T_edge = edge_feat @ off-diagonal slots, both on the Linear kernels) and one workgroup per node enumerates the node's sequences
 // itself: per sequence it sums <= L + L (L - 1) table rows, adds the bias, activates and accumulates.  Nothing of size P is stored.
+// DMPLRP (models/dmplrp.py:180-185) pools the same contraction with no activation and no factor in between; its collapsed index
+// (the distinct table rows of every ego with their occurrence counts over the sequences of dataset.py:1843-1886) is built below.
 //
 // Ego index (built once per batch): uptr / unbr / ueid = the duplicate-free, sorted out-neighbour lists over
 // the edges that count (is_reversed == 0) with the LAST edge id of every (u, w); per node {kind, dummy neighbours}, the sequence
@@ -363,11 +365,212 @@ __global__ __launch_bounds__(kThreads) void lrp_pool_kernel(LrpPoolArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------- collapsed index (DMPLRP)
+// models/dmplrp.py:180-185 pools the contracted sequences of a node with nothing non-linear in between, so the pooled row is a
+// weighted sum of table rows: out[v] = sum_rows (occurrences of the row in v's sequences) T[row].  The occurrence counts have
+// closed forms in the ego's kind, its d neighbours (nd of them dummies) and the sorted positions of the nodes involved; nothing is
+// enumerated and nothing is sized by the sequence count.  Rows are numbered as the composed path numbers them: node u at position
+// k -> u L + k, edge eid in slot (a, b) -> N L + eid L (L - 1) + lrp_off_slot(a, b).
+struct LrpForm {
+    int kind, m;                 // positions 1 .. m hold (kind 2: non-dummy) neighbours; kind 2 puts a dummy neighbour at m + 1
+    int64_t d, nd, nn, total;
+};
+
+__device__ __forceinline__ int64_t cl_perm(int64_t n, int k) {       // n (n - 1) .. (n - k + 1), 0 when there is none
+    if (k < 0 || n < k) return 0;
+    int64_t r = 1;
+    for (int i = 0; i < k; ++i) r *= n - i;
+    return r;
+}
+
+__device__ __forceinline__ int64_t cl_comb(int64_t n, int k) {       // C(n, k), k <= 3
+    if (k < 0 || n < k) return 0;
+    if (k == 0) return 1;
+    if (k == 1) return n;
+    const int64_t c2 = n * (n - 1) / 2;
+    if (k == 2) return c2;
+    return c2 % 3 == 0 ? c2 / 3 * (n - 2) : c2 * ((n - 2) / 3);
+}
+
+__device__ __forceinline__ LrpForm lrp_form(int kind, int L, int64_t d, int64_t nd, int64_t total) {
+    LrpForm f;
+    f.kind = kind; f.d = d; f.nd = nd; f.nn = d - nd; f.total = total;
+    const int64_t room = kind == 2 ? L - 2 : L - 1, have = kind == 2 ? f.nn : d;
+    f.m = (int)(room < have ? room : have);
+    return f;
+}
+
+// sequences of the ego that hold its neighbour of sorted position t (t < 0: the ego's own node; z: the neighbour is a dummy) at k
+__device__ __forceinline__ int64_t lrp_form_node(const LrpForm& f, int64_t t, bool z, int k) {
+    if (t < 0) return k == 0 ? f.total : 0;
+    if (k < 1) return 0;
+    if (f.kind == 0) return k <= f.m ? cl_perm(f.d - 1, f.m - 1) : 0;
+    if (f.kind == 1) return k <= f.m ? cl_comb(t, k - 1) * cl_comb(f.d - 1 - t, f.m - k) : 0;
+    if (z) return k == f.m + 1 ? cl_perm(f.nn, f.m) : 0;
+    return k <= f.m ? f.nd * cl_perm(f.nn - 1, f.m - 1) : 0;
+}
+
+// sequences that hold neighbour ta at position a AND neighbour tb at position b (a != b, ta != tb)
+__device__ __forceinline__ int64_t lrp_form_joint(const LrpForm& f, int64_t ta, bool za, int a, int64_t tb, bool zb, int b) {
+    if (ta < 0) return a == 0 ? lrp_form_node(f, tb, zb, b) : 0;
+    if (tb < 0) return b == 0 ? lrp_form_node(f, ta, za, a) : 0;
+    if (a < 1 || b < 1) return 0;
+    const int m = f.m;
+    if (f.kind == 0) return (a <= m && b <= m) ? cl_perm(f.d - 2, m - 2) : 0;
+    if (f.kind == 1) {
+        if (ta > tb) {
+            const int64_t t = ta; ta = tb; tb = t;
+            const int p = a; a = b; b = p;
+        }
+        if (!(a < b && b <= m)) return 0;
+        return cl_comb(ta, a - 1) * cl_comb(tb - ta - 1, b - a - 1) * cl_comb(f.d - 1 - tb, m - b);
+    }
+    if (za && zb) return 0;
+    if (!za && !zb) return (a <= m && b <= m) ? f.nd * cl_perm(f.nn - 2, m - 2) : 0;
+    const int pn = za ? b : a, pz = za ? a : b;                    // the non-dummy's and the dummy's position
+    return (pz == m + 1 && pn <= m) ? cl_perm(f.nn - 1, m - 1) : 0;
+}
+
+template <int L, typename F>
+__device__ __forceinline__ void lrp_edge_rows(const LrpForm& f, int64_t NL, int32_t eid, int64_t ta, bool za, int64_t tb, bool zb, F&& emit) {
+#pragma unroll
+    for (int a = 0; a < L; ++a)
+#pragma unroll
+        for (int b = 0; b < L; ++b) {
+            if (a == b) continue;
+            const int64_t c = lrp_form_joint(f, ta, za, a, tb, zb, b);
+            if (c > 0) emit(NL + (int64_t)eid * (L * (L - 1)) + lrp_off_slot<L>(a, b), c);
+        }
+}
+
+// Candidate c of the ego of v (d neighbours), 3 d + 1 in all: c <= d the node rows of local node c (0 = v); d < c <= 2 d the
+// edge v -> neighbour c - d - 1; 2 d < c <= 3 d the edges of neighbour c - 2 d - 1 into the ego (its own list walked and searched
+// for in v's, or v's walked and looked up in its own, whichever list is shorter).
+template <int L, typename F>
+__device__ __forceinline__ void lrp_collapse_candidate(const LrpIndex& ix, const uint8_t* __restrict__ dummy, int64_t N, int32_t v,
+                                                       int32_t base, int32_t d, const LrpForm& f, int64_t c, F&& emit) {
+    const int64_t NL = N * L;
+    if (c <= d) {
+        const int64_t t = c - 1;
+        const int32_t node = t < 0 ? v : ix.unbr[base + t];
+        const bool z = t >= 0 && dummy != nullptr && dummy[node];
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            const int64_t cnt = lrp_form_node(f, t, z, k);
+            if (cnt > 0) emit((int64_t)node * L + k, cnt);
+        }
+        return;
+    }
+    if (c <= 2 * (int64_t)d) {
+        const int64_t t = c - d - 1;
+        const bool z = dummy != nullptr && dummy[ix.unbr[base + t]];
+        lrp_edge_rows<L>(f, NL, ix.ueid[base + t], -1, false, t, z, emit);
+        return;
+    }
+    const int64_t t = c - 2 * (int64_t)d - 1;
+    const int32_t u = ix.unbr[base + t];
+    const bool zu = dummy != nullptr && dummy[u];
+    const int32_t ub = ix.uptr[u], du = ix.uptr[u + 1] - ub;
+    if (du <= d) {
+        for (int32_t j = 0; j < du; ++j) {
+            const int32_t w = ix.unbr[ub + j];
+            int64_t tb = -1;
+            if (w != v) {
+                int32_t lo = base, hi = base + d;
+                while (lo < hi) {
+                    const int32_t mid = (lo + hi) >> 1;
+                    if (ix.unbr[mid] < w) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo >= base + d || ix.unbr[lo] != w) continue;
+                tb = lo - base;
+            }
+            lrp_edge_rows<L>(f, NL, ix.ueid[ub + j], t, zu, tb, tb >= 0 && dummy != nullptr && dummy[w], emit);
+        }
+    } else {
+        const int32_t e0 = lrp_lookup(ix, u, v);
+        if (e0 >= 0) lrp_edge_rows<L>(f, NL, e0, t, zu, -1, false, emit);
+        for (int32_t tb = 0; tb < d; ++tb) {
+            if (tb == t) continue;
+            const int32_t w = ix.unbr[base + tb];
+            const int32_t e = lrp_lookup(ix, u, w);
+            if (e >= 0) lrp_edge_rows<L>(f, NL, e, t, zu, tb, dummy != nullptr && dummy[w], emit);
+        }
+    }
+}
+
+// exclusive scan of one value per thread over the workgroup; total = the sum
+__device__ __forceinline__ int64_t lrp_block_scan(int64_t val, int64_t* s, int64_t& total) {
+    const int tid = threadIdx.x;
+    s[tid] = val;
+    __syncthreads();
+    for (int off = 1; off < kThreads; off <<= 1) {
+        const int64_t add = tid >= off ? s[tid - off] : 0;
+        __syncthreads();
+        s[tid] += add;
+        __syncthreads();
+    }
+    total = s[kThreads - 1];
+    const int64_t excl = s[tid] - val;
+    __syncthreads();
+    return excl;
+}
+
+// One workgroup per node, one candidate per thread and round (a hub's 3 d + 1 candidates are spread over the 256 threads).  The
+// count pass sums the entries of every candidate; the fill pass gives every candidate its slot from a workgroup scan -- no
+// atomics, so two builds store the same lists -- and evaluates it again to store.  The rows of a node come out in candidate order;
+// the caller sorts them.
+template <int L, bool FILL>
+__global__ __launch_bounds__(kThreads) void lrp_collapse_kernel(int64_t N, LrpIndex ix, const uint8_t* __restrict__ dummy,
+                                                                 int64_t* __restrict__ col_count, const int32_t* __restrict__ col_ptr,
+                                                                 int32_t* __restrict__ col_rows, int64_t* __restrict__ col_cnt) {
+    __shared__ int64_t s_scan[kThreads];
+    const int32_t v = blockIdx.x, tid = threadIdx.x;
+    const int32_t base = ix.uptr[v], d = ix.uptr[v + 1] - base;
+    const LrpForm f = lrp_form(ix.ego[2 * v], L, d, ix.ego[2 * v + 1], ix.count[v]);
+    const int64_t C = 3 * (int64_t)d + 1;
+    int64_t mine = 0, total = 0;
+    int64_t run = FILL ? col_ptr[v] : 0;
+    const int64_t end = FILL ? col_ptr[v + 1] : 0;
+    for (int64_t c0 = 0; c0 < C; c0 += kThreads) {
+        const int64_t c = c0 + tid;
+        int64_t n = 0;
+        if (c < C) lrp_collapse_candidate<L>(ix, dummy, N, v, base, d, f, c, [&](int64_t, int64_t) { ++n; });
+        if (!FILL) {
+            mine += n;
+            continue;
+        }
+        int64_t pos = run + lrp_block_scan(n, s_scan, total);
+        if (n > 0)
+            lrp_collapse_candidate<L>(ix, dummy, N, v, base, d, f, c, [&](int64_t row, int64_t cnt) {
+                if (pos < end) {
+                    col_rows[pos] = (int32_t)row;
+                    col_cnt[pos] = cnt;
+                }
+                ++pos;
+            });
+        run += total;
+    }
+    if (!FILL) {
+        lrp_block_scan(mine, s_scan, total);
+        if (tid == 0) col_count[v] = total;
+    }
+}
+
 int check_index(int64_t N, int32_t L, const LrpIndex& ix) {
     DN_REQUIRE(N >= 0 && N < INT32_MAX, "dn_lrp: bad sizes (N = %lld)", (long long)N);
     DN_REQUIRE(L >= 2 && L <= 4, "dn_lrp: the sequence length must be 2, 3 or 4 (got %d)", L);
     if (N == 0) return DN_OK;
     DN_REQUIRE(ix.uptr && ix.ego && ix.count, "dn_lrp: NULL pointer");
+    return DN_OK;
+}
+
+int check_collapse(int64_t N, int64_t E, int32_t L, const LrpIndex& ix) {
+    if (int rc = check_index(N, L, ix)) return rc;
+    DN_REQUIRE(E >= 0 && N * L + E * L * (L - 1) < INT32_MAX, "dn_lrp_collapse: %lld nodes and %lld edges: the table rows do not fit int32",
+               (long long)N, (long long)E);
+    if (N == 0) return DN_OK;
+    DN_REQUIRE(E == 0 || (ix.unbr && ix.ueid), "dn_lrp_collapse: NULL pointer");
     return DN_OK;
 }
 
@@ -422,6 +625,39 @@ int dn_lrp_perm_fill_i32(int64_t N, int32_t L, const int32_t* uptr, const int32_
     if (L == 2) hipLaunchKernelGGL(lrp_perm_fill_kernel<2>, grid, block, 0, st, N, P, ix, perm_ptr, perm_nodes, perm_edges);
     else if (L == 3) hipLaunchKernelGGL(lrp_perm_fill_kernel<3>, grid, block, 0, st, N, P, ix, perm_ptr, perm_nodes, perm_edges);
     else hipLaunchKernelGGL(lrp_perm_fill_kernel<4>, grid, block, 0, st, N, P, ix, perm_ptr, perm_nodes, perm_edges);
+    DN_CHECK_LAUNCH();
+    return DN_OK;
+}
+
+int dn_lrp_collapse_count_i32(int64_t N, int64_t E, int32_t L, const int32_t* uptr, const int32_t* unbr, const int32_t* ueid,
+                              const int32_t* upos, const int32_t* ego, const int64_t* count, const uint8_t* dummy, int64_t* col_count,
+                              dn_stream_t stream) {
+    LrpIndex ix{uptr, unbr, ueid, upos, ego, count};
+    if (int rc = check_collapse(N, E, L, ix)) return rc;
+    if (N == 0) return DN_OK;
+    DN_REQUIRE(col_count != nullptr, "dn_lrp_collapse_count: NULL pointer");
+    const dim3 grid((unsigned)N), block(kThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (L == 2) hipLaunchKernelGGL((lrp_collapse_kernel<2, false>), grid, block, 0, st, N, ix, dummy, col_count, nullptr, nullptr, nullptr);
+    else if (L == 3) hipLaunchKernelGGL((lrp_collapse_kernel<3, false>), grid, block, 0, st, N, ix, dummy, col_count, nullptr, nullptr, nullptr);
+    else hipLaunchKernelGGL((lrp_collapse_kernel<4, false>), grid, block, 0, st, N, ix, dummy, col_count, nullptr, nullptr, nullptr);
+    DN_CHECK_LAUNCH();
+    return DN_OK;
+}
+
+int dn_lrp_collapse_fill_i32(int64_t N, int64_t E, int32_t L, const int32_t* uptr, const int32_t* unbr, const int32_t* ueid,
+                             const int32_t* upos, const int32_t* ego, const int64_t* count, const uint8_t* dummy, const int32_t* col_ptr,
+                             int64_t Q, int32_t* col_rows, int64_t* col_cnt, dn_stream_t stream) {
+    LrpIndex ix{uptr, unbr, ueid, upos, ego, count};
+    if (int rc = check_collapse(N, E, L, ix)) return rc;
+    DN_REQUIRE(Q >= 0 && Q < INT32_MAX, "dn_lrp_collapse_fill: %lld rows do not fit an int32 index", (long long)Q);
+    if (N == 0 || Q == 0) return DN_OK;
+    DN_REQUIRE(col_ptr && col_rows && col_cnt, "dn_lrp_collapse_fill: NULL pointer");
+    const dim3 grid((unsigned)N), block(kThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (L == 2) hipLaunchKernelGGL((lrp_collapse_kernel<2, true>), grid, block, 0, st, N, ix, dummy, nullptr, col_ptr, col_rows, col_cnt);
+    else if (L == 3) hipLaunchKernelGGL((lrp_collapse_kernel<3, true>), grid, block, 0, st, N, ix, dummy, nullptr, col_ptr, col_rows, col_cnt);
+    else hipLaunchKernelGGL((lrp_collapse_kernel<4, true>), grid, block, 0, st, N, ix, dummy, nullptr, col_ptr, col_rows, col_cnt);
     DN_CHECK_LAUNCH();
     return DN_OK;
 }

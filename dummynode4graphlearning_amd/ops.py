@@ -80,7 +80,7 @@ def _ws(nbytes, device):
 # raw launches
 # ----------------------------------------------------------------------------------------------
 def gather_segsum(x, idx=None, ptr_=None, num_segments=None, scale=None, self_in=None, self_coef=0.0,
-                  mean=False, out=None):
+                  mean=False, out=None, tag="gather_segsum"):
     """out[s] = self_coef*self_in[s] + sum_{i in [ptr[s],ptr[s+1])} scale[i] * x[idx[i]]  (dn_gather_segsum_*)."""
     require_gpu(x, idx, ptr_, scale, self_in, out)
     assert x.dim() == 2
@@ -110,7 +110,7 @@ def gather_segsum(x, idx=None, ptr_=None, num_segments=None, scale=None, self_in
         check(fn(ptr(x), x.shape[0], H, ptr(idx), ptr(scale), ptr(ptr_), S, M, ptr(out), ptr(self_in),
                  float(self_coef), 1 if mean else 0, stream_ptr()), "dn_gather_segsum")
 
-    launch_tagged("gather_segsum", _launch)
+    launch_tagged(tag, _launch)
     return out
 
 
@@ -3471,6 +3471,35 @@ class lrp_composed(lrp_fused):
         super().__init__(not on)
 
 
+# The default path of ops.lrp_pool_linear (the pooling of a DMPLRP layer): the collapsed index (LrpIndex.collapsed) or
+# lrp_pool(act="none", factor=None).  Measured in docs/LAB_NOTES.md "DMPLRP" (L = 4, H = 64): level with the composed path on the
+# config-3 scale batch (op 2.32 against 2.41 ms, the layer step inside the spread), 2.3 against 15.9 ms per layer step on 64-node
+# graphs with a forward-connected dummy node -- so the collapsed path is the default.
+LRP_COLLAPSED_DEFAULT = True
+
+
+def lrp_collapsed_enabled():
+    m = getattr(_lrp_tls, "collapsed", None)
+    return LRP_COLLAPSED_DEFAULT if m is None else m
+
+
+class lrp_collapsed:
+    """Context manager: ops.lrp_pool_linear calls started inside it (on this thread) pool over the collapsed index (on=True) or
+    through ops.lrp_pool(act="none", factor=None) (on=False: the composed or fused path, as ops.lrp_fused / lrp_composed say)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_lrp_tls, "collapsed", None)
+        _lrp_tls.collapsed = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _lrp_tls.collapsed = self.old
+        return False
+
+
 def lrp_fused_supported(H):
     return 16 <= int(H) <= LRP_MAX_H and int(H) % 16 == 0
 
@@ -3479,6 +3508,15 @@ class LrpPermIndex(NamedTuple):
     perm_ptr: torch.Tensor       # [N + 1] int32
     perm_nodes: torch.Tensor     # [P, L] int32, -1 = empty
     perm_edges: torch.Tensor     # [P, L * L] int32, -1 = empty
+
+
+class LrpCollapsed(NamedTuple):
+    col_ptr: torch.Tensor        # [N + 1] int32
+    col_rows: torch.Tensor       # [Q] int32: per node the distinct table rows of its sequences, ascending
+    col_cnt: torch.Tensor        # [Q] int64: the occurrences of the row in the node's sequences
+    col_node: torch.Tensor       # [Q] int32: the node of every entry
+    tptr: torch.Tensor           # [rows + 1] int32: the same entries grouped by table row (the backward's lists) ...
+    tperm: torch.Tensor          # [Q] int32: ... as positions into col_rows / col_cnt / col_node
 
 
 class LrpIndex:
@@ -3527,6 +3565,8 @@ class LrpIndex:
         self._perm = None
         self._composed = None
         self._total = None
+        self._collapsed = None
+        self._collapsed_scale = {}
 
     def _args(self):
         return (ptr(self.uptr), ptr(self.unbr), ptr(self.ueid), ptr(self.upos), ptr(self.ego), ptr(self.count))
@@ -3577,6 +3617,54 @@ class LrpIndex:
             tptr, tperm = csr_build(idx, N * L + E * L * (L - 1))
             self._composed = (idx, ptr_, tptr, seg.index_select(0, tperm.long()).contiguous())
         return self._composed
+
+
+    def table_rows(self):
+        """Rows of the stacked table [T_node; T_edge] of composed_tables / collapsed."""
+        return self.num_nodes * self.seq_len + self.num_edges * self.seq_len * (self.seq_len - 1)
+
+    def collapsed(self):
+        """The collapsed index (LrpCollapsed) of dmplrp.py:180-185, kept: per node the distinct rows of the stacked table that its
+        sequences touch (numbered as composed_tables numbers them) with their occurrence counts, from the closed forms of
+        dn_lrp_collapse_*_i32 by count -> scan -> fill, then one device sort that makes the rows of a node ascend.  Nothing is sized
+        by the sequence count; reads the entry total Q back once."""
+        if self._collapsed is None:
+            N, E, L, dev = self.num_nodes, self.num_edges, self.seq_len, self.uptr.device
+            R = self.table_rows()
+            if R > _INT32_MAX:
+                raise _lib.DnHipError("LRP index: %d table rows do not fit an int32 index" % R)
+            per_node = torch.zeros(N, dtype=torch.long, device=dev)
+            check(lib().dn_lrp_collapse_count_i32(N, E, L, *self._args(), ptr(self.dummy), ptr(per_node), stream_ptr()),
+                  "dn_lrp_collapse_count_i32")
+            ptr64 = torch.cat([per_node.new_zeros(1), torch.cumsum(per_node, 0)])
+            Q = int(ptr64[-1])
+            if Q > _INT32_MAX:
+                raise _lib.DnHipError("LRP index: %d collapsed rows do not fit an int32 index" % Q)
+            col_ptr = ptr64.to(I32)
+            rows = torch.empty(Q, dtype=I32, device=dev)
+            cnt = torch.empty(Q, dtype=torch.long, device=dev)
+            check(lib().dn_lrp_collapse_fill_i32(N, E, L, *self._args(), ptr(self.dummy), ptr(col_ptr), Q, ptr(rows), ptr(cnt),
+                                                 stream_ptr()), "dn_lrp_collapse_fill_i32")
+            node = torch.repeat_interleave(torch.arange(N, device=dev, dtype=I32), per_node, output_size=Q)
+            order = torch.sort(node.long() * max(R, 1) + rows.long())[1]          # distinct keys: the order is unique
+            rows, cnt = rows.index_select(0, order).contiguous(), cnt.index_select(0, order).contiguous()
+            tptr, tperm = csr_build(rows, R)
+            self._collapsed = LrpCollapsed(col_ptr, rows, cnt, node, tptr, tperm)
+        return self._collapsed
+
+    def collapsed_scale(self, pool):
+        """(scale [Q], its transposed order, the transposed node list) of ops.lrp_pool_linear: occurrences / P_v, divided in
+        double and rounded to fp32, for pool = "mean"; the occurrences for "sum"."""
+        if pool not in self._collapsed_scale:
+            c = self.collapsed()
+            if pool == "mean":
+                scale = (c.col_cnt.double() / self.count.index_select(0, c.col_node.long()).double()).float()
+            else:
+                scale = c.col_cnt.float()
+            t = c.tperm.long()
+            self._collapsed_scale[pool] = (scale.contiguous(), scale.index_select(0, t).contiguous(),
+                                           c.col_node.index_select(0, t).contiguous())
+        return self._collapsed_scale[pool]
 
 
 def _lrp_index_of(graph, seq_len):
@@ -3659,6 +3747,18 @@ def _lrp_act(t, act):
     return t
 
 
+def _lrp_tables(x, edge_feat, weight, L):
+    """(T_node [N, L H], T_edge [E, L (L - 1) H], H): the weight [in, H, L^2] row-factorised on the Linear kernels."""
+    require_gpu(x.contiguous(), edge_feat.contiguous())
+    H = int(weight.shape[1])
+    wt = weight.permute(2, 1, 0)                                          # [L * L, H, in]
+    diag = [k * (L + 1) for k in range(L)]
+    off = [s for s in range(L * L) if s % (L + 1) != 0]
+    t_node = linear_any(x, wt[diag].reshape(L * H, -1))                   # [N, L * H]
+    t_edge = linear_any(edge_feat, wt[off].reshape(L * (L - 1) * H, -1))  # [E, L * (L - 1) * H]
+    return t_node, t_edge, H
+
+
 def lrp_pool(x, edge_feat, weight, bias, factor, graph, seq_len=4, act="relu", pool="mean"):
     """[N, H] = act(pool_p(act(sum_slots W_slot^T row_slot + bias)) * factor) of lrp.py:65-75 without its [P L^2, in] tensor.
     x [N, in], edge_feat [E, in], weight [in, H, L^2] (the reference's parameter), bias [H] or None, factor [N, H] or None (then no
@@ -3676,13 +3776,7 @@ def lrp_pool(x, edge_feat, weight, bias, factor, graph, seq_len=4, act="relu", p
         raise _lib.DnHipError("lrp_pool: weight [in, H, L * L] with in = the width of x and edge_feat expected")
     if x.shape[0] != ix.num_nodes or edge_feat.shape[0] != ix.num_edges:
         raise _lib.DnHipError("lrp_pool: one x row per node and one edge_feat row per edge of the indexed batch expected")
-    require_gpu(x.contiguous(), edge_feat.contiguous())
-    H = int(weight.shape[1])
-    wt = weight.permute(2, 1, 0)                                          # [L * L, H, in]
-    diag = [k * (L + 1) for k in range(L)]
-    off = [s for s in range(L * L) if s % (L + 1) != 0]
-    t_node = linear_any(x, wt[diag].reshape(L * H, -1))                   # [N, L * H]
-    t_edge = linear_any(edge_feat, wt[off].reshape(L * (L - 1) * H, -1))  # [E, L * (L - 1) * H]
+    t_node, t_edge, H = _lrp_tables(x, edge_feat, weight, L)
     forced = getattr(_lrp_tls, "fused", None)
     fused = (LRP_FUSED_DEFAULT or not ix.materialisable()) if forced is None else forced
     if fused and lrp_fused_supported(H) and x.dtype == torch.float32:
@@ -3695,3 +3789,45 @@ def lrp_pool(x, edge_feat, weight, bias, factor, graph, seq_len=4, act="relu", p
         z = z + bias
     out = segment_reduce(_lrp_act(z, act), ix.perm_index().perm_ptr, pool)
     return out if factor is None else _lrp_act(out * factor, act)
+
+
+class _WeightedSegsumFn(torch.autograd.Function):
+    """out[s] = sum of scale[i] x[idx[i]] over segment s (gather_segsum); backward: the same kernel over the transposed lists,
+    every sum in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, x, idx, ptr_, scale, tptr, tseg, tscale):
+        ctx.tables, ctx.rows = (tptr, tseg, tscale), x.shape[0]
+        return gather_segsum(x.contiguous(), idx, ptr_, scale=scale, tag="lrp_collapsed")
+
+    @staticmethod
+    def backward(ctx, g):
+        tptr, tseg, tscale = ctx.tables
+        return (gather_segsum(g.contiguous(), tseg, tptr, ctx.rows, scale=tscale, tag="lrp_collapsed_bwd"),) + (None,) * 6
+
+
+def lrp_pool_linear(x, edge_feat, weight, bias, graph, seq_len=4, pool="mean"):
+    """[N, H] = pool_p(sum_slots W_slot^T row_slot + bias) of dmplrp.py:180-185: lrp_pool without activation and factor, where the
+    pooling commutes with the sum over the slots.  The same row-factorised tables as lrp_pool, then ONE weighted gather_segsum over
+    the collapsed index (LrpIndex.collapsed: per node the distinct table rows of its sequences, scale = occurrences / P_v for
+    "mean", occurrences for "sum"), + bias (mean) or + P_v bias (sum); the backward runs the same kernel over the transposed lists,
+    so both directions are deterministic.  Any width gather_segsum takes.  `with ops.lrp_collapsed(False):` runs
+    lrp_pool(act="none", factor=None) instead (ops.LRP_COLLAPSED_DEFAULT)."""
+    if pool not in ("mean", "sum"):
+        raise ValueError("lrp_pool_linear: pool in mean | sum (got %s)" % pool)
+    if not lrp_collapsed_enabled():
+        return lrp_pool(x, edge_feat, weight, bias, None, graph, seq_len, act="none", pool=pool)
+    ix = _lrp_index_of(graph, seq_len)
+    L = ix.seq_len
+    if weight.dim() != 3 or weight.shape[2] != L * L or x.shape[1] != weight.shape[0] or edge_feat.shape[1] != weight.shape[0]:
+        raise _lib.DnHipError("lrp_pool_linear: weight [in, H, L * L] with in = the width of x and edge_feat expected")
+    if x.shape[0] != ix.num_nodes or edge_feat.shape[0] != ix.num_edges:
+        raise _lib.DnHipError("lrp_pool_linear: one x row per node and one edge_feat row per edge of the indexed batch expected")
+    t_node, t_edge, H = _lrp_tables(x, edge_feat, weight, L)
+    col = ix.collapsed()
+    scale, tscale, tnode = ix.collapsed_scale(pool)
+    table = torch.cat([t_node.reshape(-1, H), t_edge.reshape(-1, H)], 0)
+    out = _WeightedSegsumFn.apply(table, col.col_rows, col.col_ptr, scale, col.tptr, tnode, tscale)
+    if bias is None:
+        return out
+    return out + bias if pool == "mean" else out + ix.count.to(out.dtype).unsqueeze(1) * bias

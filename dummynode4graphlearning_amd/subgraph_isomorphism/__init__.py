@@ -8,3 +8,4 @@ from .graph_adj import (EquivariantEmbedding, GraphAdjModel, MultihotEmbedding, 
                         OutputDict, PositionEmbedding, RGCN, RGIN, ScalarFilter, UniformEmbedding)
 from .graph_adj_v2 import CompGCN, DMPNN, GraphAdjModelV2  # noqa: F401
 from .lrp import LRP, LRPLayer  # noqa: F401
+from .dmplrp import DMPLRP, DMPLRPPoolLayer  # noqa: F401

@@ -199,11 +199,13 @@ class DMPLayer(nn.Module):
         names = ("in_weight", "out_weight", "src_weight", "dst_weight", "nloop_weight", "eloop_weight")
         for n in names:
             setattr(self, n, nn.Parameter(th.empty(input_dim, hidden_dim)))
+        self._create_extra_weights()
         if bias:
             self.nbias, self.ebias = nn.Parameter(th.empty(hidden_dim)), nn.Parameter(th.empty(hidden_dim))
         else:
             self.register_parameter("nbias", None)
             self.register_parameter("ebias", None)
+        self._create_extra_bias(bias)
 
         def mlp():
             mods = []
@@ -220,6 +222,7 @@ class DMPLayer(nn.Module):
         self.drop = nn.Dropout(dropout)
         for n in names:
             init_weight(getattr(self, n), activation=act_func, init="uniform")
+        self._init_extra_weights()
         for seq in (self.nmlp, self.emlp):
             for m in seq.modules():
                 if isinstance(m, nn.Linear):
@@ -233,6 +236,17 @@ class DMPLayer(nn.Module):
                 getattr(self, n).data.div_(init_neigenv)
             for n in ("src_weight", "dst_weight", "eloop_weight"):
                 getattr(self, n).data.div_(init_eeigenv)
+
+    # hooks of a layer that adds parameters of its own (DMPLRPPoolLayer): the reference registers and initialises them between
+    # this layer's, and both the state_dict order and the random stream follow the order
+    def _create_extra_weights(self):
+        pass
+
+    def _create_extra_bias(self, bias):
+        pass
+
+    def _init_extra_weights(self):
+        pass
 
     def _run(self, seq, h):
         if len(seq) == 0:

@@ -961,6 +961,21 @@ int dn_lrp_ego_index_i32(int64_t N, int32_t L, const int32_t* uptr, const int32_
 int dn_lrp_perm_fill_i32(int64_t N, int32_t L, const int32_t* uptr, const int32_t* unbr, const int32_t* ueid, const int32_t* upos,
                          const int32_t* ego, const int64_t* count, const int32_t* perm_ptr, int64_t P, int32_t* perm_nodes,
                          int32_t* perm_edges, dn_stream_t stream);
+/* The collapsed index of DMPLRP (subgraph_isomorphism/models/dmplrp.py:180-185: the contraction of the sequences of
+ * dataset.py:1843-1886 is pooled with nothing non-linear in between, so the pooled row of a node is a weighted sum of table rows).
+ * Per node the distinct table rows its sequences touch, each with its number of occurrences, from closed forms in the ego index
+ * (nothing is enumerated or sized by the sequence count).  Rows: node u at position k -> u L + k; edge eid in slot (a, b), a != b
+ * -> N L + eid L (L - 1) + a (L - 1) + (b > a ? b - 1 : b); N L + E L (L - 1) must fit int32.  count -> scan -> fill:
+ *     dn_lrp_collapse_count_i32   col_count [N] int64 = the rows of every node
+ *     dn_lrp_collapse_fill_i32    col_rows [Q] int32 / col_cnt [Q] int64 for col_ptr [N + 1] = the exclusive scan of col_count
+ * Slots come from workgroup scans (no atomics: two builds store the same lists); the rows of a node are stored in the kernel's
+ * candidate order, not ascending.  dummy (uint8 [N]) may be NULL.  The index must be free of self-loops (dn_lrp_ego_index_i32). */
+int dn_lrp_collapse_count_i32(int64_t N, int64_t E, int32_t L, const int32_t* uptr, const int32_t* unbr, const int32_t* ueid,
+                              const int32_t* upos, const int32_t* ego, const int64_t* count, const uint8_t* dummy, int64_t* col_count,
+                              dn_stream_t stream);
+int dn_lrp_collapse_fill_i32(int64_t N, int64_t E, int32_t L, const int32_t* uptr, const int32_t* unbr, const int32_t* ueid,
+                             const int32_t* upos, const int32_t* ego, const int64_t* count, const uint8_t* dummy, const int32_t* col_ptr,
+                             int64_t Q, int32_t* col_rows, int64_t* col_cnt, dn_stream_t stream);
 /* LDS budget of the pooling kernels: an ego of d + 1 nodes keeps its T_node rows in LDS when (d + 1) L H 4 <= dn_lrp_stage_bytes()
  * and its pair -> edge table when d + 1 <= dn_lrp_pair_nodes(); larger egos read through L2. */
 int32_t dn_lrp_stage_bytes(void);
