@@ -168,6 +168,9 @@ _SIGS = {
     "dn_lrp_pair_nodes": (c_i32, []),
     "dn_lrp_pool_fwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32] + [P] * 10 + [c_i32, c_i32, c_f32, P, P, P]),
     "dn_lrp_pool_bwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32] + [P] * 10 + [c_i32, c_i32, c_f32] + [P] * 6 + [P]),
+    "dn_hgt_attn_fwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, c_i32] + [P] * 10 + [c_f32, P, P, P]),
+    "dn_hgt_attn_bwd_dst_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, c_i32] + [P] * 10 + [c_f32] + [P] * 5 + [P]),
+    "dn_hgt_attn_bwd_src_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, c_i32] + [P] * 9 + [P]),
 }
 
 _lib = None

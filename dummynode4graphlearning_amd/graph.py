@@ -23,11 +23,13 @@ class _IndexCache:
         self._edge_index = None
         self._rel = []  # [(etype tensor, version, num_rels, RelIndex)]
         self._lrp = {}  # {sequence length: ops.LrpIndex}
+        self._hgt = []  # [(key tensor, version, tag, ops.HgtIndex / ops.TypeIndex)]
 
     def clear(self):
         self._edge_index = None
         self._rel = []
         self._lrp = {}
+        self._hgt = []
 
 
 class BatchedGraph:
@@ -153,6 +155,25 @@ class BatchedGraph:
                               dummy=self.ndata.get("is_dummy"), node_ptr=self.node_ptr())
             self._cache._lrp[int(seq_len)] = ix
         return ix
+
+    def _hgt_cached(self, key, tag, build):
+        for t, ver, g, ix in self._cache._hgt:
+            if t is key and ver == key._version and g == tag:
+                return ix
+        ix = build()
+        self._cache._hgt.append((key, key._version, tag, ix))
+        if len(self._cache._hgt) > 4:
+            self._cache._hgt.pop(0)
+        return ix
+
+    def hgt_index(self, etype, num_rels):
+        """Cached ops.HgtIndex (the edges sorted by (destination, edge type), the reverse CSR over that order) of the HGT model."""
+        return self._hgt_cached(etype, ("edges", int(num_rels)),
+                                lambda: ops.HgtIndex(self._src, self._dst, etype, self._n, num_rels))
+
+    def type_index(self, ntype, num_types):
+        """Cached ops.TypeIndex (the nodes grouped by type) for the typed row products of the HGT model."""
+        return self._hgt_cached(ntype, ("nodes", int(num_types)), lambda: ops.TypeIndex(ntype, num_types))
 
     # ---- dgl.batch (dataset.py:1321-1328, 1609-1610) ----------------------------------------------
     @staticmethod

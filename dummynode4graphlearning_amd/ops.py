@@ -3831,3 +3831,319 @@ def lrp_pool_linear(x, edge_feat, weight, bias, graph, seq_len=4, pool="mean"):
     if bias is None:
         return out
     return out + bias if pool == "mean" else out + ix.count.to(out.dtype).unsqueeze(1) * bias
+
+
+# ----------------------------------------------------------------------------------------------
+# HGT: rows times the weight of their node type, and the edge-softmax attention (dn_hgt.hip)
+# ----------------------------------------------------------------------------------------------
+HGT_MAX_H = 256
+HGT_HEADS = (1, 2, 4, 8)
+_hgt_tls = _threading.local()
+
+# The layers' default.  Measured on the scale batch (docs/LAB_NOTES.md "SI count models: HGT"; H = 64, 4 heads, 14 relations, 25.6 k
+# nodes, 155 k edges, fused and composed alternated in one process): the layer step 1.72 against 2.54 ms, the model step 10.4 against
+# 12.5 ms, every fused round faster than every composed round -- outside the spread, so the fused kernels are the default (unlike
+# LRP_FUSED_DEFAULT / DUAL_FUSED_DEFAULT, whose gains stayed inside it).
+HGT_FUSED_DEFAULT = True
+
+
+def hgt_fused_enabled():
+    m = getattr(_hgt_tls, "fused", None)
+    return HGT_FUSED_DEFAULT if m is None else m
+
+
+class hgt_fused:
+    """Context manager: HeteroGraphTransLayer forwards started inside it (on this thread) run their attention on dn_hgt.hip (on=True)
+    where hgt_fused_supported allows it, or on the composed path (on=False: torch scatter ops over the same factorisation)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_hgt_tls, "fused", None)
+        _hgt_tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _hgt_tls.fused = self.old
+        return False
+
+
+def hgt_fused_supported(x, heads):
+    """The predicate of the fused attention: fp32 rows on the GPU, heads in {1, 2, 4, 8}, H <= 256, H / heads a multiple of 4."""
+    H, heads = int(x.shape[-1]), int(heads)
+    return (x.is_cuda and x.dtype == torch.float32 and heads in HGT_HEADS and H <= HGT_MAX_H and H % heads == 0
+            and (H // heads) % 4 == 0)
+
+
+class TypeIndex:
+    """The rows of a batch grouped by an integer type (the node label): perm / inv between the given and the grouped order and
+    the tile / chunk tables of the any-width grouped products (dn_rows_gemm_* / dn_rows_wgrad_any_*).  Built once per batch."""
+
+    def __init__(self, types, num_types):
+        require_gpu(types)
+        T, n = int(num_types), int(types.numel())
+        t = types.reshape(-1).long()
+        if n:
+            lo, hi = (int(v) for v in torch.aminmax(t))
+            if lo < 0 or hi >= T:
+                raise _lib.DnHipError("node type out of [0, %d): min %d, max %d" % (T, lo, hi))
+        self.num_types, self.num_rows = T, n
+        self.perm = torch.argsort(t, stable=True)
+        self.inv = torch.empty_like(self.perm)
+        self.inv[self.perm] = torch.arange(n, device=t.device)
+        cnt = torch.bincount(t, minlength=T)
+        tptr = torch.cat([cnt.new_zeros(1), torch.cumsum(cnt, 0)]).to(I32)
+        self.type_ptr = tptr
+        self.tiles = build_row_tables(tptr, T, n, 64)
+        self.chunks = build_row_tables(tptr, T, n, 1024, want_ptr=True)
+
+
+class _TypedLinearFn(torch.autograd.Function):
+    """y[i] = x[i] @ W[type_i] for any widths: the rows grouped by type, one dn_rows_gemm_* launch; backward one launch for d x and
+    the deterministic split-K weight gradient (dn_rows_wgrad_any_*)."""
+
+    @staticmethod
+    def forward(ctx, x, W, tix):
+        xs = x.index_select(0, tix.perm)
+        y = rows_gemm(xs, W, tix.tiles).index_select(0, tix.inv)
+        ctx.tix = tix
+        ctx.save_for_backward(xs, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        xs, W = ctx.saved_tensors
+        tix = ctx.tix
+        gs = g.index_select(0, tix.perm)
+        gx = gW = None
+        if ctx.needs_input_grad[0]:
+            gx = rows_gemm(gs, W, tix.tiles, transpose_w=True).index_select(0, tix.inv)
+        if ctx.needs_input_grad[1]:
+            gW = rows_wgrad_any(xs, gs, tix.chunks, W.shape[0])
+        return gx, gW, None
+
+
+def typed_linear(x, W, types, tix=None):
+    """x [N, K] times W[type of the row] ([T, K, M]) -> [N, M].  fp32 / bf16 on the GPU: the grouped product kernels over a
+    TypeIndex (tix, or built here from `types`); anything else: the gathered torch product."""
+    if x.is_cuda and x.dim() == 2 and x.dtype == W.dtype and x.dtype in MFMA_DTYPES and x.shape[0] > 0:
+        return _TypedLinearFn.apply(x, W, tix if tix is not None else TypeIndex(types, W.shape[0]))
+    return torch.bmm(x.unsqueeze(1), W.index_select(0, types.reshape(-1).long())).squeeze(1)
+
+
+class HgtIndex:
+    """The edges of a batch sorted by (destination, edge type), the non-empty (destination, edge type) PAIRS numbered in that order,
+    and the reverse CSR by source over the sorted order (int32, device).  pair_ptr [P + 1] bounds the edges of a pair, dst_ptr
+    [N + 1] the pairs of a destination (consecutive), pair_rel [P] is the pair's type.  The per-pair tensors of the layer (Qp, U and
+    their gradients) live in ROWS grouped by edge type -- the order of the relation-grouped products, so nothing is permuted between
+    the products and the attention: pair_row [P] is a pair's row, row_dst / row_rel [P] name the pair of a row, row_s [E] is the row
+    of an edge's pair.  Built once per batch with torch sorts and scans."""
+
+    def __init__(self, src, dst, etype, num_nodes, num_rels):
+        require_gpu(src, dst, etype)
+        N, R, E = int(num_nodes), int(num_rels), int(src.numel())
+        _check_edge_types(etype, R)
+        self.num_nodes, self.num_rels, self.num_edges = N, R, E
+        src, dst, etype = src.reshape(-1).long(), dst.reshape(-1).long(), etype.reshape(-1).long()
+        if dst.numel() != E or etype.numel() != E:
+            raise _lib.DnHipError("HgtIndex: src, dst and etype must have one entry per edge")
+        if E:                                                                  # (the kernels index rows by these: checked once per batch)
+            lo, hi = (int(v) for v in torch.aminmax(torch.stack([src, dst])))
+            if lo < 0 or hi >= N:
+                raise _lib.DnHipError("HgtIndex: node id out of [0, %d): min %d, max %d" % (N, lo, hi))
+        dev = src.device
+        key = dst * R + etype
+        self.perm = torch.argsort(key, stable=True)
+        key_s = key.index_select(0, self.perm)
+        self.src_l, self.dst_l = src.index_select(0, self.perm), dst.index_select(0, self.perm)
+        self.et_l = etype.index_select(0, self.perm)
+        pair_key, pair_l, cnt = torch.unique_consecutive(key_s, return_inverse=True, return_counts=True)
+        P = int(pair_key.numel())
+        self.num_pairs = P
+        zero = torch.zeros(1, dtype=torch.long, device=dev)
+        self.pair_ptr = torch.cat([zero, torch.cumsum(cnt, 0)]).to(I32)
+        pair_dst = torch.div(pair_key, R, rounding_mode="floor")
+        pair_rel = pair_key - pair_dst * R
+        self.pair_rel = pair_rel.to(I32)
+        self.dst_ptr = torch.cat([zero, torch.cumsum(torch.bincount(pair_dst, minlength=N), 0)]).to(I32)
+        self.src_s, self.et_s = self.src_l.to(I32), self.et_l.to(I32)
+        if P:
+            t = self.pair_types = TypeIndex(self.pair_rel, R)                  # rows: the pairs grouped by edge type
+            pair_row = t.inv
+            self.row_dst_l, self.row_rel_l = pair_dst.index_select(0, t.perm), pair_rel.index_select(0, t.perm)
+        else:
+            self.pair_types = None
+            pair_row = self.row_dst_l = self.row_rel_l = pair_dst
+        self.pair_row = pair_row.to(I32)
+        self.row_l = pair_row.index_select(0, pair_l)
+        self.row_s = self.row_l.to(I32)
+        operm = torch.argsort(self.src_l, stable=True)
+        self.out_ptr = torch.cat([zero, torch.cumsum(torch.bincount(src, minlength=N), 0)]).to(I32)
+        self.out_pos = operm.to(I32)
+        self.out_row = self.row_s.index_select(0, operm).contiguous()
+        self._pri_csr = None
+
+    def pri_csr(self):
+        """The rows of every edge type (contiguous) as a _SplitCSR: the fixed-order sum of the per-pair partials of d relation_pri."""
+        if self._pri_csr is None:
+            rows = torch.arange(self.num_pairs, dtype=I32, device=self.pair_rel.device)
+            self._pri_csr = _SplitCSR(self.pair_types.type_ptr, rows, self.num_rels)
+        return self._pri_csr
+
+
+class _HgtPairExpandFn(torch.autograd.Function):
+    """Qp [P, H] (rows grouped by edge type): Qp[row] = q[row_dst[row]] @ W[row_rel[row]] -- one row gather, ONE relation-grouped product
+    (dn_rows_gemm_*).  Backward: the transposed product, the sum over the pairs of every destination (a gather over pair_row), and
+    the deterministic split-K weight gradient."""
+
+    @staticmethod
+    def forward(ctx, q, W, ix):
+        xs = q.index_select(0, ix.row_dst_l)
+        ctx.ix = ix
+        ctx.save_for_backward(xs, W)
+        return rows_gemm(xs, W, ix.pair_types.tiles)
+
+    @staticmethod
+    def backward(ctx, g):
+        xs, W = ctx.saved_tensors
+        ix = ctx.ix
+        t = ix.pair_types
+        g = g.contiguous()
+        gq = gW = None
+        if ctx.needs_input_grad[0]:
+            gq = gather_segsum(rows_gemm(g, W, t.tiles, transpose_w=True), ix.pair_row, ix.dst_ptr, ix.num_nodes)
+        if ctx.needs_input_grad[1]:
+            gW = rows_wgrad_any(xs, g, t.chunks, W.shape[0])
+        return gq, gW, None
+
+
+class _HgtPairReduceFn(torch.autograd.Function):
+    """agg [N, H]: agg[d] = sum over the pairs p of d of U[pair_row[p]] @ W[pair_rel[p]] (one relation-grouped product over the rows,
+    one segment sum)."""
+
+    @staticmethod
+    def forward(ctx, U, W, ix):
+        ctx.ix = ix
+        ctx.save_for_backward(U, W)
+        return gather_segsum(rows_gemm(U, W, ix.pair_types.tiles), ix.pair_row, ix.dst_ptr, ix.num_nodes)
+
+    @staticmethod
+    def backward(ctx, g):
+        U, W = ctx.saved_tensors
+        ix = ctx.ix
+        t = ix.pair_types
+        gs = g.index_select(0, ix.row_dst_l)                                                # d Y, row by row
+        gU = gW = None
+        if ctx.needs_input_grad[0]:
+            gU = rows_gemm(gs, W, t.tiles, transpose_w=True)
+        if ctx.needs_input_grad[1]:
+            gW = rows_wgrad_any(U, gs, t.chunks, W.shape[0])
+        return gU, gW, None
+
+
+def _hgt_products_on_kernels(x, W, ix):
+    return x.is_cuda and x.dtype == W.dtype and x.dtype in MFMA_DTYPES and ix.num_pairs > 0
+
+
+def hgt_pair_expand(q, W, ix):
+    """Qp [P, H] = q[row_dst] @ W[row_rel] (W [R, H, H]; rows grouped by edge type, see HgtIndex)."""
+    if _hgt_products_on_kernels(q, W, ix):
+        return _HgtPairExpandFn.apply(q.contiguous(), W.contiguous(), ix)
+    return torch.bmm(q.index_select(0, ix.row_dst_l).unsqueeze(1), W.index_select(0, ix.row_rel_l)).squeeze(1)
+
+
+def hgt_pair_reduce(U, W, ix):
+    """agg [N, H] = sum over the pairs of every destination of U[row] @ W[row_rel[row]] (W [R, H, H])."""
+    if _hgt_products_on_kernels(U, W, ix):
+        return _HgtPairReduceFn.apply(U.contiguous(), W.contiguous(), ix)
+    Y = torch.bmm(U.unsqueeze(1), W.index_select(0, ix.row_rel_l)).squeeze(1)
+    return torch.zeros((ix.num_nodes, W.shape[2]), dtype=Y.dtype, device=Y.device).index_add(0, ix.row_dst_l, Y)
+
+
+class _HgtAttnFn(torch.autograd.Function):
+    """U [P, H] of dn_hgt_attn_fwd_f32 from Qp [P, H] (both in HgtIndex rows), k, v [N, H] and pri [R, heads]; backward: dn_hgt_attn_bwd_dst_f32 (d Qp, the
+    per-pair partials of d pri, summed here per edge type in a fixed order) and dn_hgt_attn_bwd_src_f32 (d k, d v).  Deterministic."""
+
+    @staticmethod
+    def forward(ctx, Qp, k, v, pri, ix, heads, scale):
+        Qp, k, v, pri = Qp.contiguous(), k.contiguous(), v.contiguous(), pri.contiguous()
+        require_gpu(Qp, k, v, pri)
+        N, R, E, P, H = ix.num_nodes, ix.num_rels, ix.num_edges, ix.num_pairs, int(k.shape[1])
+        if Qp.shape != (P, H) or k.shape != (N, H) or v.shape != (N, H) or pri.shape != (R, heads):
+            raise _lib.DnHipError("hgt_attention: Qp [P, H], k / v [N, H] and pri [R, heads] expected")
+        U = torch.empty((P, H), dtype=torch.float32, device=k.device)
+        att = torch.empty((E, heads), dtype=torch.float32, device=k.device)
+        launch_tagged("hgt_attn_fwd", lambda: check(lib().dn_hgt_attn_fwd_f32(
+            N, E, P, H, heads, ptr(ix.dst_ptr), ptr(ix.pair_ptr), ptr(ix.pair_row), ptr(ix.src_s), ptr(ix.et_s), ptr(ix.row_s), ptr(Qp), ptr(k),
+            ptr(v), ptr(pri), float(scale), ptr(att), ptr(U), stream_ptr()), "dn_hgt_attn_fwd_f32"))
+        ctx.ix, ctx.heads, ctx.scale = ix, int(heads), float(scale)
+        ctx.save_for_backward(Qp, k, v, pri, att)
+        return U
+
+    @staticmethod
+    def backward(ctx, dU):
+        Qp, k, v, pri, att = ctx.saved_tensors
+        ix, heads, scale = ctx.ix, ctx.heads, ctx.scale
+        N, R, E, P, H = ix.num_nodes, ix.num_rels, ix.num_edges, ix.num_pairs, int(k.shape[1])
+        dU = dU.contiguous()
+        dev = k.device
+        dl = torch.empty((E, heads), dtype=torch.float32, device=dev)
+        dQp = torch.empty_like(Qp)
+        part = torch.empty((P, heads), dtype=torch.float32, device=dev)
+        launch_tagged("hgt_attn_bwd_dst", lambda: check(lib().dn_hgt_attn_bwd_dst_f32(
+            N, E, P, H, heads, ptr(ix.dst_ptr), ptr(ix.pair_ptr), ptr(ix.pair_rel), ptr(ix.pair_row), ptr(ix.src_s), ptr(ix.row_s), ptr(Qp), ptr(k),
+            ptr(v), ptr(pri), scale, ptr(att), ptr(dU), ptr(dl), ptr(dQp), ptr(part), stream_ptr()), "dn_hgt_attn_bwd_dst_f32"))
+        dk, dv = torch.empty_like(k), torch.empty_like(v)
+        launch_tagged("hgt_attn_bwd_src", lambda: check(lib().dn_hgt_attn_bwd_src_f32(
+            N, E, P, H, heads, ptr(ix.out_ptr), ptr(ix.out_pos), ptr(ix.out_row), ptr(Qp), ptr(dU), ptr(att), ptr(dl), ptr(dk), ptr(dv),
+            stream_ptr()), "dn_hgt_attn_bwd_src_f32"))
+        dpri = ix.pri_csr().segsum(part) if P else torch.zeros_like(pri)
+        return dQp, dk, dv, dpri, None, None, None
+
+
+def hgt_attention_composed(Qp, k, v, pri, ix, heads, scale):
+    """The same U [P, H] from torch gathers and scatter ops over the sorted edge list (any dtype; its sums are atomic adds)."""
+    N, E, P, H = ix.num_nodes, ix.num_edges, ix.num_pairs, int(k.shape[1])
+    dk = H // heads
+    q_e = Qp.reshape(P, heads, dk).index_select(0, ix.row_l)
+    k_e = k.reshape(N, heads, dk).index_select(0, ix.src_l)
+    logit = (q_e * k_e).sum(-1) * pri.index_select(0, ix.et_l) * scale                                   # [E, heads]
+    didx = ix.dst_l.view(-1, 1).expand(E, heads)
+    mx = torch.full((N, heads), float("-inf"), dtype=logit.dtype, device=logit.device)
+    mx = mx.scatter_reduce(0, didx, logit.detach(), "amax", include_self=True)
+    p = torch.exp(logit - mx.index_select(0, ix.dst_l))
+    sm = torch.zeros((N, heads), dtype=p.dtype, device=p.device).index_add(0, ix.dst_l, p)
+    a = p / sm.index_select(0, ix.dst_l)
+    msg = (a.unsqueeze(-1) * v.reshape(N, heads, dk).index_select(0, ix.src_l)).reshape(E, H)
+    return torch.zeros((P, H), dtype=msg.dtype, device=msg.device).index_add(0, ix.row_l, msg)
+
+
+def hgt_attention(Qp, k, v, pri, ix, heads, scale):
+    """U [P, H]: per (destination, edge type) pair the softmax-weighted sum of the value rows over the pair's edges, the softmax
+    running over ALL in-edges of the destination per head with logits <Qp[pair], k[src]> pri[et] scale.  The fused kernels
+    (dn_hgt.hip) where hgt_fused_enabled() and hgt_fused_supported, else the composed path."""
+    if hgt_fused_enabled() and hgt_fused_supported(k, heads) and Qp.dtype == v.dtype == pri.dtype == torch.float32:
+        return _HgtAttnFn.apply(Qp, k, v, pri, ix, int(heads), float(scale))
+    return hgt_attention_composed(Qp, k, v, pri, ix, int(heads), float(scale))
+
+
+def block_diag_dense(blocks):
+    """[..., B, si, so] -> [..., B si, B so] with the blocks on the diagonal, zeros elsewhere (torch, differentiable)."""
+    B, si, so = blocks.shape[-3:]
+    eye = torch.eye(B, dtype=blocks.dtype, device=blocks.device).view(B, 1, B, 1)
+    return (blocks.unsqueeze(-2) * eye).reshape(blocks.shape[:-3] + (B * si, B * so))
+
+
+def hgt_message_pass(q, k, v, att, msg, pri, ix, scale):
+    """agg [N, H] of an HGT layer (hgt.py:252-264, 324-333): per destination and head the softmax over its in-edges of
+    <q_dst, k_src @ att[et]> pri[et] scale, then the sum of a_e (v_src @ msg[et]).  q, k, v [N, H]; att, msg [R, heads, d_k, d_k];
+    pri [R, heads]; ix an HgtIndex.  The relation matrices are applied on the destination side, once per (destination, edge type)
+    pair that has an edge: Qp[p] = q_dst @ blockdiag(att[r])^T (hgt_pair_expand), the attention (hgt_attention) yields the weighted
+    value sums U[p] per pair, and agg[d] = sum over the pairs of d of U[p] @ blockdiag(msg[r]) (hgt_pair_reduce)."""
+    heads = int(att.shape[1])
+    w_att = block_diag_dense(att.transpose(-1, -2))                  # Qp[p, (h, j)] = sum_i q[(h, i)] att[r, h, j, i]
+    w_msg = block_diag_dense(msg)                                    # agg[(h, i)] += sum_j U[p, (h, j)] msg[r, h, j, i]
+    Qp = hgt_pair_expand(q, w_att, ix)
+    U = hgt_attention(Qp, k.contiguous(), v.contiguous(), pri, ix, heads, scale)
+    return hgt_pair_reduce(U, w_msg, ix)

@@ -9,3 +9,4 @@ from .graph_adj import (EquivariantEmbedding, GraphAdjModel, MultihotEmbedding, 
 from .graph_adj_v2 import CompGCN, DMPNN, GraphAdjModelV2  # noqa: F401
 from .lrp import LRP, LRPLayer  # noqa: F401
 from .dmplrp import DMPLRP, DMPLRPPoolLayer  # noqa: F401
+from .hgt import HGT, DecompMultiTransform, HeteroGraphTransLayer  # noqa: F401

@@ -998,6 +998,33 @@ int dn_lrp_pool_bwd_f32(int64_t N, int64_t E, int32_t H, int32_t L, const int32_
                         const float* bias, const float* factor, int32_t pool_mean, int32_t act_on, float slope, const float* pooled,
                         const float* g, float* d_tnode, float* d_tedge, float* d_bias, float* d_factor, dn_stream_t stream);
 
+/* ---- HGT edge-softmax attention of the SI count model HGT (dn_hgt.hip) ----
+ * The edges sorted by (destination, edge type).  A pair is a (destination, edge type) with at least one edge, numbered in that
+ * order: dst_ptr [N + 1] bounds the pairs of every destination, pair_ptr [P + 1] the edges of every pair, pair_rel [P] is the pair's
+ * edge type.  The per-pair tensors are stored grouped by edge type (the order of the relation-grouped products): pair_row [P] is
+ * the row of a pair; src_s / et_s / row_s [E] are the source, the type and the pair's row of every edge in sorted order.
+ * Qp [P, H] holds the query of the pair's destination already multiplied by the type's block-diagonal attention matrix, K / V
+ * [N, H] the plain key and value rows, pri [R, heads].  Per destination and head
+ *     logit_e = <Qp[row_e, h], K[src_e, h]> * pri[et_e, h] * scale,   a = softmax over ALL in-edges of dst (max subtracted)
+ *     att [E, heads] = a (sorted order),   U [P, H]: U[pair_row[p]] = sum over the edges of pair p of a_e * V[src_e]
+ * One workgroup per destination, nothing of size E x H is stored.  heads in {1, 2, 4, 8}, H <= 256, H / heads a multiple of 4.
+ * N == 0: returns 0 without a launch. */
+int dn_hgt_attn_fwd_f32(int64_t N, int64_t E, int64_t P, int32_t H, int32_t heads, const int32_t* dst_ptr, const int32_t* pair_ptr,
+                        const int32_t* pair_row, const int32_t* src_s, const int32_t* et_s, const int32_t* row_s, const float* Qp,
+                        const float* K, const float* V, const float* pri, float scale, float* att, float* U, dn_stream_t stream);
+/* Backward in destination order from dU [P, H]: dl [E, heads] = the gradient of the raw dot products (softmax backward
+ * a (da - sum a da), times pri and scale), dQp [P, H], and dpri_part [P, heads] = every pair's partial of d pri, both at the
+ * pair's row (the caller sums the rows of each type).  No atomics. */
+int dn_hgt_attn_bwd_dst_f32(int64_t N, int64_t E, int64_t P, int32_t H, int32_t heads, const int32_t* dst_ptr, const int32_t* pair_ptr,
+                            const int32_t* pair_rel, const int32_t* pair_row, const int32_t* src_s, const int32_t* row_s, const float* Qp,
+                            const float* K, const float* V, const float* pri, float scale, const float* att, const float* dU, float* dl,
+                            float* dQp, float* dpri_part, dn_stream_t stream);
+/* Backward in source order over the reverse CSR out_ptr [N + 1] with, per entry, the edge's position in the destination order
+ * (out_pos) and the row of its pair (out_row): dK[s] = sum dl_e Qp[row_e], dV[s] = sum a_e dU[row_e].  No atomics. */
+int dn_hgt_attn_bwd_src_f32(int64_t N, int64_t E, int64_t P, int32_t H, int32_t heads, const int32_t* out_ptr, const int32_t* out_pos,
+                            const int32_t* out_row, const float* Qp, const float* dU, const float* att, const float* dl, float* dK,
+                            float* dV, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
