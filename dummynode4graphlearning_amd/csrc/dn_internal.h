@@ -12,6 +12,11 @@ int launch_transform_ring256(const void* X, const void* X2, int32_t n1, const in
                              int32_t relu, int32_t nt_store, const void* mask_pos, const int32_t* tiles, int64_t num_tiles,
                              int64_t tiles_per_wg, void* Y, int32_t w_kn, float slope, hipStream_t st);
 
+// ... the dense form (rows in order, W [k][n], no epilogue) over tiles {0, beg, end, s0 | s1 << 8} that also writes per tile the
+// in-order fp32 sum of its rows beg + s0 .. beg + s1 - 1, rounded to bf16, to seg_sums [num_tiles, 256] (dn_layer_chain_dgrad_bf16)
+int launch_transform_ring256_seg(const void* X, const void* W_kn, const int32_t* tiles, int64_t num_tiles, void* Y, void* seg_sums,
+                                 hipStream_t st);
+
 // dn_chain2.hip: dn_rows_chain2_bf16 at H == 256 (LDS-DMA ring, 8 waves, results straight from the accumulators).  Serves the
 // forward (no masks; both sign-bit outputs or neither) and the backward (both masks, no sign-bit outputs) forms.
 bool chain2_ring_supported(bool has_mask0, bool has_mask1, bool has_bits1, bool has_bits2);

@@ -86,11 +86,17 @@ __device__ int32_t g_zero_idx[64];     // row 0 (device globals are zero-initial
 
 #define DN_DS_READ128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
 
-template <bool MASK, bool IDX, bool EPI, bool HASX2>
+// SEG (the dense form only: rows in order, one source, no epilogue): a tile's record carries s0 | s1 << 8 in its fourth word and the
+// launch also writes, per tile, the sum of its rows beg + s0 .. beg + s1 - 1 to seg_out [num_tiles, 256] -- taken by the LOADERS (one
+// column a lane, 4 x 64 = 256) from the landed stage, row by row in fp32 from zero and rounded once: dn_gather_segsum_bf16's order
+// over a contiguous list.  A loader sums tiles t, t + 1 behind the barrier of their pair, after it has requested tiles t + 6, t + 7:
+// the stages are its own to read until the next barrier but one, and at HBM pace a pair of tiles leaves it more than twice the time.
+template <bool MASK, bool IDX, bool EPI, bool HASX2, bool SEG = false>
 __global__ __launch_bounds__(kThreads) void rows_transform_ring_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ X2, int32_t n1, const int32_t* __restrict__ idx,
     const bf16_t* __restrict__ Wn, const bf16_t* __restrict__ bias, int32_t flags, const bf16_t* __restrict__ mask_pos,
-    const Tile* __restrict__ tiles, int32_t num_tiles, int32_t tiles_per_wg, bf16_t* __restrict__ Y, float slope) {
+    const Tile* __restrict__ tiles, int32_t num_tiles, int32_t tiles_per_wg, bf16_t* __restrict__ Y, float slope,
+    bf16_t* __restrict__ seg_out) {
     __shared__ __attribute__((aligned(1024))) char lds[kNS * kStageB];
     __shared__ __attribute__((aligned(16))) int32_t descL[kDescRing][4]; // tile records for the compute waves (copied by loader 0)
     __shared__ __attribute__((aligned(128))) int32_t recR[kLoaders][kRecRing][4];            // loader-private rings: tile records
@@ -202,6 +208,30 @@ __global__ __launch_bounds__(kThreads) void rows_transform_ring_kernel(
 #pragma unroll
             for (int j = 0; j < kDmaPerTile; ++j) glds16(src[j], st + (unsigned)(2 * j) * kRowB);   // lane l lands at + 16 l
         };
+        // SEG: the in-order column sums of rows s0 .. s1 - 1 of tile u (landed and visible: behind the barrier of its pair), column
+        // 64 q + lane: LDS (row r, position p ^ (r & 15)) holds piece p of the row.  Eight reads in flight, added in row order.
+        auto seg_sum = [&](int u) {
+            const int32_t* rp = &recR[q][u % kRecRing][0];
+            const int rows_u = __builtin_amdgcn_readfirstlane(min(max(rp[2] - rp[1], 0), kTR));
+            const int sg = __builtin_amdgcn_readfirstlane(rp[3]);
+            const int s0 = sg & 0xff, s1 = min((sg >> 8) & 0xff, rows_u);
+            const char* stg = lds + (u % kNS) * kStageB + (lane & 7) * 2;
+            const int p = 8 * q + (lane >> 3);
+            float acc = 0.f;
+#pragma unroll 1
+            for (int r = s0; r < s1; r += 8) {
+                uint32_t v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int rr = min(r + k, kTR - 1);
+                    v[k] = *reinterpret_cast<const uint16_t*>(stg + rr * kRowB + ((p ^ (rr & 15)) << 4));
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (r + k < s1) acc += __uint_as_float(v[k] << 16);
+            }
+            seg_out[(size_t)(t_beg + u) * kH + 64 * q + lane] = (bf16_t)acc;
+        };
         auto batch = [&](int u) {                                          // u = 8 b: indices of batch b + 1, records of batch b + 2
             if ((u & (kBatch - 1)) == 0) {                                 // wave-uniform
                 stage_idx(u + kBatch);
@@ -247,6 +277,10 @@ __global__ __launch_bounds__(kThreads) void rows_transform_ring_kernel(
             batch(t + kNS);
             prep(t + kNS, srcA);
             prep(t + kNS + 1, srcB);
+            if constexpr (SEG) {                                           // (the two stores count in vmcnt behind this pair's DMAs: the
+                seg_sum(t);                                                //  wait at the top only gets stricter)
+                if (t + 1 < nt) seg_sum(t + 1);
+            }
             DN_STAT(st_vm, a1 - a0); DN_STAT(st_bar, a2 - a1); DN_STAT(st_body, DN_STAMP() - a2);
         }
         wait_vmcnt<0>();                                                   // nothing may land after the LDS is given back
@@ -490,7 +524,8 @@ int launch_transform_ring256(const void* X_, const void* X2, int32_t n1, const i
 #define DN_RING_LAUNCH(M, I, E, X)                                                                                      \
     hipLaunchKernelGGL((rows_transform_ring_kernel<M, I, E, X>), dim3((unsigned)grid), dim3(kThreads), 0, st, (const bf16_t*)X_, \
                        (const bf16_t*)X2, n1, idx, (const bf16_t*)Wn, (const bf16_t*)bias, flags, (const bf16_t*)mask_pos,      \
-                       reinterpret_cast<const Tile*>(tiles), (int32_t)num_tiles, (int32_t)tiles_per_wg, (bf16_t*)Y, slope)
+                       reinterpret_cast<const Tile*>(tiles), (int32_t)num_tiles, (int32_t)tiles_per_wg, (bf16_t*)Y, slope,      \
+                       (bf16_t*)nullptr)
     // the conv's launches (gathered rows, no epilogue, one source) get the leanest instruction stream: the loop is bound by
     // vector-instruction issue, not by the matrix pipe (~180 VALU instructions per SIMD and tile before this split)
     const bool epi = bias != nullptr || relu != 0;
@@ -507,6 +542,19 @@ int launch_transform_ring256(const void* X_, const void* X2, int32_t n1, const i
         else DN_RING_LAUNCH(false, false, true, false);
     }
 #undef DN_RING_LAUNCH
+    DN_CHECK_LAUNCH();
+    return DN_OK;
+}
+
+int launch_transform_ring256_seg(const void* X, const void* W_kn, const int32_t* tiles, int64_t num_tiles, void* Y, void* seg_sums,
+                                 hipStream_t st) {
+    const int64_t tiles_per_wg = dn_cdiv(num_tiles, 256);                  // one persistent workgroup per CU
+    const int64_t grid = dn_cdiv(num_tiles, tiles_per_wg);
+    const int32_t flags = 2 | 4;                                           // streaming stores, W as the parameter stores it ([k][n])
+    hipLaunchKernelGGL((rows_transform_ring_kernel<false, false, false, false, true>), dim3((unsigned)grid), dim3(kThreads), 0, st,
+                       (const bf16_t*)X, (const bf16_t*)nullptr, 0x7fffffff, (const int32_t*)nullptr, (const bf16_t*)W_kn,
+                       (const bf16_t*)nullptr, flags, (const bf16_t*)nullptr, reinterpret_cast<const Tile*>(tiles), (int32_t)num_tiles,
+                       (int32_t)tiles_per_wg, (bf16_t*)Y, 0.f, (bf16_t*)seg_sums);
     DN_CHECK_LAUNCH();
     return DN_OK;
 }

@@ -1838,11 +1838,11 @@ FOLD_ENABLED = _os.environ.get("DN_FOLD", "1") != "0"
 class _Fold:
     """Tables of one folded relation: rows [beg, end) of the row set, one per segment (graph)."""
     __slots__ = ("rel", "beg", "end", "n", "fold_info", "part_ptr", "num_parts", "main_tiles", "sweep_tiles", "add_idx",
-                 "graph_tiles", "multi")
+                 "graph_tiles", "multi", "seg_tiles")
 
     def __init__(self, ix, direction, cand):
         self.rel, self.beg, self.end, self.n = cand
-        self.fold_info = self.part_ptr = self.graph_tiles = self.multi = None
+        self.fold_info = self.part_ptr = self.graph_tiles = self.multi = self.seg_tiles = None
         self.num_parts = int(2 * self.n + ix.num_nodes // 32 + 1)   # upper bound of part_ptr[-1] without a read-back: every segment
         #                                                             starts one partial row, every tile boundary inside one another
         self.main_tiles = None                               # plain relation-major tiles, built on first use (_conv_tiles_for)
@@ -2637,6 +2637,142 @@ def rgin_layer_wide(x, W, W_loop, bias, linears, slope, index_set):
     """The whole RGIN layer of rgin_layer_wide_ok's case as one autograd function (_RginLayerWideFn)."""
     return _RginLayerWideFn.apply(x, float(slope), index_set, W, W_loop, bias, linears[0].weight, linears[0].bias,
                                   linears[1].weight, linears[1].bias)
+
+
+# DN_LAYER_CHAIN_WGRAD=0: an H = 256 bf16 RGIN layer on a large batch stays a chain of separate autograd functions (conv, MLP) whose
+# backward takes Linear 1's weight gradient from its own pass over the rows of h (dn_mlp_bwd_fused_bf16's second launch) instead of
+# deriving it from the conv's (_RginLayerChainFn: step 2.991 -> 2.892 ms on one box, docs/LAB_NOTES.md round 8) -- for A/B runs and the tests
+LAYER_CHAIN_WGRAD_ENABLED = _os.environ.get("DN_LAYER_CHAIN_WGRAD", "1") != "0"
+
+
+def _chain_seg_tiles(ix, fold):
+    """Tile table of dn_layer_chain_dgrad_bf16 for the backward fold of an index whose every graph fits one tile: per graph
+    {0, first node, end node, s0 | s1 << 8} with [s0, s1) = where the graph's aux_b list (a contiguous ascending run: the fold's
+    verdict) lies inside the tile.  Built on first use (a few elementwise launches, no read-back), kept on the fold."""
+    if fold.seg_tiles is None:
+        n, v = fold.n, ix.dirs["b"]
+        tp, ap = fold.graph_tiles[0][:n + 1], v.aux_ptr[:n + 1]
+        beg, end = tp[:n], tp[1:]
+        s0 = v.aux_idx[ap[:n].long()] - beg
+        seg = s0 | ((s0 + (ap[1:] - ap[:n])) << 8)
+        fold.seg_tiles = torch.stack([torch.zeros_like(beg), beg, end, seg], 1).to(I32).contiguous()
+    return fold.seg_tiles
+
+
+def layer_chain_dgrad(g1, w1, seg_tiles):
+    """g0 = g1 @ w1 (w1: Linear.weight as stored, [out, in]) on the dense ring transform over seg_tiles (_chain_seg_tiles), and from
+    the same pass the bf16 sums of g1 over every tile's segment in row order (dn_layer_chain_dgrad_bf16).  -> (g0, sums [T, H]).
+    g0 is bit-identical to mlp_bwd_fused's unmasked g_next, the sums to gather_segsum over the same lists."""
+    g1, w1 = g1.contiguous(), w1.contiguous()
+    require_gpu(g1, w1, seg_tiles)
+    N, H = g1.shape
+    T = int(seg_tiles.shape[0])
+    assert g1.dtype == torch.bfloat16 and w1.dtype == g1.dtype and H == 256 and tuple(w1.shape) == (H, H)
+    assert seg_tiles.dtype == I32 and seg_tiles.dim() == 2 and seg_tiles.shape[1] == 4 and seg_tiles.is_contiguous()
+    g0 = torch.empty_like(g1)
+    sums = torch.empty((T, H), dtype=g1.dtype, device=g1.device)
+
+    def _launch():
+        check(lib().dn_layer_chain_dgrad_bf16(ptr(g1), ptr(w1), N, H, ptr(seg_tiles), T, ptr(g0), ptr(sums), stream_ptr()),
+              "dn_layer_chain_dgrad_bf16")
+    launch_tagged("chain_dgrad", _launch)
+    return g0, sums
+
+
+def layer_chain_wgrad_combine(M, c, w1, W, W_loop, bias):
+    """The parameter gradients of the conv and of Linear 1 from M [R + 1, H, H] = A_r^T g1 (fp32, the self loop last) and c = colsum(g1)
+    (fp32 [H]): dWc_r = M_r w1, db = c w1, dW1 = sum_r M_r^T Wc_r + c b^T, db1 = c  (dn_layer_chain_wgrad_combine; bf16 out of fp64
+    sums of the exact products, one rounding each, fixed order).  -> (dWc [R + 1, H, H], db [H] or None, dW1 [H, H], db1 [H])."""
+    M, c, w1, W, W_loop = M.contiguous(), c.contiguous(), w1.contiguous(), W.contiguous(), W_loop.contiguous()
+    require_gpu(M, c, w1, W, W_loop, bias)
+    R, H = W.shape[0], 256
+    assert M.dtype == torch.float32 and tuple(M.shape) == (R + 1, H, H) and c.dtype == torch.float32 and c.numel() == H
+    assert w1.dtype == torch.bfloat16 and tuple(w1.shape) == (H, H) and W.dtype == w1.dtype and tuple(W.shape[1:]) == (H, H)
+    assert W_loop.dtype == w1.dtype and tuple(W_loop.shape) == (H, H)
+    assert bias is None or (bias.dtype == w1.dtype and bias.numel() == H and bias.is_contiguous())
+    dev = M.device
+    dWc = torch.empty((R + 1, H, H), dtype=w1.dtype, device=dev)
+    dW1 = torch.empty((H, H), dtype=w1.dtype, device=dev)
+    db = torch.empty((H,), dtype=w1.dtype, device=dev) if bias is not None else None
+    db1 = torch.empty((H,), dtype=w1.dtype, device=dev)
+    ws = _ws(lib().dn_layer_chain_wgrad_combine_workspace_bytes(R, H), dev)
+
+    def _launch():
+        check(lib().dn_layer_chain_wgrad_combine(ptr(M), ptr(c), ptr(w1), ptr(W), ptr(W_loop), ptr(bias), R, H, ptr(dWc), ptr(db), ptr(dW1),
+                                                 ptr(db1), ptr(ws), ws.numel(), stream_ptr()), "dn_layer_chain_wgrad_combine")
+    launch_tagged("chain_combine", _launch)
+    return dWc, db, dW1, db1
+
+
+def rgin_layer_chain_ok(x, W, W_loop, bias, linears, index_set):
+    """Can a whole RGIN layer run as _RginLayerChainFn?  bf16, H = 256, square, self loop, conv bias, two square Linears with biases,
+    x wants a gradient, a batch of at least MLP_BWD_FUSED_MIN_ROWS rows above _RginLayerWideFn's range, one index part on the
+    unit-stream closing path whose fold is absorbed by single-tile AGG units in both directions (every graph within 32 nodes)."""
+    if not (LAYER_CHAIN_WGRAD_ENABLED and MLP_BWD_FUSED_ENABLED and CHAIN2_ENABLED and W_loop is not None and bias is not None
+            and len(linears) == 2 and all(l.bias is not None for l in linears)):
+        return False
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] == 256 and W.dtype == x.dtype
+            and tuple(W.shape[1:]) == (256, 256) and tuple(W_loop.shape) == (256, 256) and W_loop.dtype == x.dtype
+            and bias.dtype == x.dtype and x.requires_grad and torch.is_grad_enabled()
+            and all(l.weight.dtype == x.dtype and l.bias.dtype == x.dtype and tuple(l.weight.shape) == (256, 256) for l in linears)):
+        return False
+    ix = index_set.index
+    N = x.shape[0]
+    if not (_selfsum_ok(ix, x) and _kn_ok(x) and N >= max(MLP_BWD_FUSED_MIN_ROWS, 1) and ix.num_rows + 2 * N > WIDE_LAYER_MAX_ROWS
+            and _close_kind(256, x.dtype) == "units" and not conv_graphs_ok(x, PassWeights(W, W_loop, kn=True), ix)):
+        return False
+    for d in ("f", "b"):
+        fold = _row_index_fold(ix, d, "units")
+        if fold is None or fold.graph_tiles is None or fold.multi is not None or not ix.close_units(d).agg:
+            return False
+    return ix.dirs["b"].n_aux == ix._fold["b"].n
+
+
+class _RginLayerChainFn(torch.autograd.Function):
+    """act(lin2(act(lin1(conv(x))))) of an RGIN layer at H = 256 in bf16 on a large batch (rgin.py:102-160 + 50-57, BASELINE config 5)
+    with the forward launches of the separate functions (_RowTransformFn + _ReluMlpFn) and a backward that never reads the conv's
+    output h: nothing lies between h and Linear 1, so with g1 = the gradient of Linear 1's output and M_r = A_r^T g1
+        dWc_r = M_r W1,  db = colsum(g1) W1,  dW1 = sum_r M_r^T Wc_r + colsum(g1) b^T,  db1 = colsum(g1)
+    -- backward = dn_mlp_bwd_fused_bf16 (layer 2, masked: dW2, db2, g1), dn_layer_chain_dgrad_bf16 (g0 = g1 W1 + the per-graph sums
+    of g1), the conv's input-gradient launches on g0 as ever, the conv's weight-gradient launch on g1 (fp32 out) and
+    dn_layer_chain_wgrad_combine: 35 products of 256^3 in place of the weight-gradient half of a pass over every row."""
+
+    @staticmethod
+    def forward(ctx, x, slope, index_set, W, W_loop, bias, w1, b1, w2, b2):
+        ctx.f32_mode = f32_mode()
+        x = x.contiguous()
+        ix = index_set.index
+        h = torch.empty_like(x)
+        aux = message_pass(x, PassWeights(W, W_loop, kn=True), bias, ix, "f", index_set.ybuf(256, x.dtype, x.device), h)
+        h1, h2, bits1, bits2 = rows_chain2(h, w1, b1, True, w2, b2, True, want_bits=True, slope=float(slope))
+        ctx.index_set, ctx.slope = index_set, float(slope)
+        ctx.save_for_backward(x, h1, bits1, bits2, W, W_loop, bias, w1, w2, aux if aux is not None else x.new_empty(0))
+        return h2
+
+    @staticmethod
+    @_backward_in_forward_mode
+    def backward(ctx, gout):
+        iset, slope = ctx.index_set, ctx.slope
+        ix = iset.index
+        x, h1, bits1, bits2, W, W_loop, bias, w1, w2, aux = ctx.saved_tensors
+        g = gout.contiguous()
+        H, R = 256, W.shape[0]
+        _, chunks = _dense_table(x.shape[0], x.device)
+        gw2, gb2, g1 = mlp_bwd_fused(g, h1, w2, chunks, mask_in_bits=bits2, mask_out_bits=bits1, slope=slope)
+        g0, g1_sums = layer_chain_dgrad(g1, w1, _chain_seg_tiles(ix, ix._fold["b"]))
+        gx = torch.empty_like(x)
+        message_pass(g0, PassWeights(W, W_loop, kn=False), None, ix, "b", iset.ybuf(H, g.dtype, g.device), gx)
+        # the conv's weight-gradient launch as ever, on g1: M_r = A_r^T g1 in fp32, c = colsum(g1) over the self-loop rows
+        M, cs = rows_wgrad(x, g1, ix.chunk_table, R + 1, idx_a=ix.row_in, idx_g=ix.row_out, A2=aux if ix.num_aux_f else None,
+                           G2=g1_sums, out_dtype=torch.float32, colsum_of=2, colsum_rel=R)
+        gAll, gb, gw1, gb1 = layer_chain_wgrad_combine(M, cs[R], w1, W, W_loop, bias)
+        return (gx, None, None, gAll[:R], gAll[R], gb, gw1, gb1, gw2, gb2.to(g.dtype))
+
+
+def rgin_layer_chain(x, W, W_loop, bias, linears, slope, index_set):
+    """The whole RGIN layer of rgin_layer_chain_ok's case as one autograd function (_RginLayerChainFn)."""
+    return _RginLayerChainFn.apply(x, float(slope), index_set, W, W_loop, bias, linears[0].weight, linears[0].bias,
+                                   linears[1].weight, linears[1].bias)
 
 
 LAYER_F32_ENABLED = _os.environ.get("DN_LAYER_F32", "1") != "0"

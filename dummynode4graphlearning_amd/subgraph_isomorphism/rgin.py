@@ -171,6 +171,10 @@ class RGINLayer(nn.Module):
         if ops.rgin_layer_wide_ok(node_feat, W, self.loop_weight, self.bias, linears, index):
             # H = 256 in bf16: the launches of the general route with ONE weight-gradient launch for the conv and both Linears
             return ops.rgin_layer_wide(node_feat, W, self.loop_weight, self.bias, linears, slope, index)
+        if ops.rgin_layer_chain_ok(node_feat, W, self.loop_weight, self.bias, linears, index):
+            # H = 256 in bf16 above the wide function's range: the launches of the general route, except that Linear 1's weight gradient
+            # comes from the conv's (no pass over the conv's output in the backward)
+            return ops.rgin_layer_chain(node_feat, W, self.loop_weight, self.bias, linears, slope, index)
         if ops.rgin_layer_f32_ok(node_feat, W, self.loop_weight, self.bias, linears, index):
             # the reference's own precision: the same launches as the separate functions, ONE weight-gradient launch in the backward
             # (residual: node_feat + layer(node_feat) leaves the MLP launch; forward_residual is told through _residual_done)

@@ -1025,6 +1025,31 @@ int dn_hgt_attn_bwd_src_f32(int64_t N, int64_t E, int64_t P, int32_t H, int32_t 
                             const int32_t* out_row, const float* Qp, const float* dU, const float* att, const float* dl, float* dK,
                             float* dV, dn_stream_t stream);
 
+/* ---- an RGIN layer's backward with Linear 1's weight gradient derived from the conv's (dn_chain_wgrad.hip; bf16, H = 256) ----
+ * Nothing lies between the conv's output h and the MLP's first Linear, so with g1 = the gradient of z1 = h W1^T + b1,
+ * M_r = A_r^T g1 (the conv's weight-gradient launch run on g1 instead of g0 = g1 W1; r = 0 .. R - 1, then the self loop) and
+ * c = colsum(g1):   dWc_r = M_r W1,  db = c W1,  dW1 = sum_r M_r^T Wc_r + c b^T,  db1 = c.
+ *
+ * dn_layer_chain_dgrad_bf16: G0 = G1 @ W_kn (the dense ring transform: bit-identical to dn_mlp_bwd_fused_bf16's g_next without
+ * masks) over `tiles` [T, 4] = {0, first row, end row, s0 | s1 << 8}: consecutive row ranges of at most 32 rows (a graph each) that
+ * cover the rows the caller wants; seg_sums [T, H] (bf16) receives per tile the sum of G1's rows first + s0 .. first + s1 - 1 taken
+ * in row order in fp32 from zero and rounded once -- dn_gather_segsum_bf16 over the same contiguous lists, from the launch
+ * that reads every G1 row anyway.  0 <= s0 <= s1 <= end - first.  N = the rows of G1 / G0 (every tile must lie inside [0, N): checked
+ * by the caller, the launch reads the table on the device).  Tiles must not be empty: a trailing run of empty tiles of a workgroup
+ * is not walked, and their rows of seg_sums stay unwritten (an empty tile in front of a live one gets a zero row). */
+int dn_layer_chain_dgrad_bf16(const void* G1, const void* W_kn, int64_t N, int32_t H, const int32_t* tiles, int64_t num_tiles, void* G0,
+                              void* seg_sums, dn_stream_t stream);
+/* dn_layer_chain_wgrad_combine: M fp32 [R + 1, H, H] (the self loop last), c fp32 [H], W1 [out, in] as nn.Linear stores it, Wc
+ * [R, in, out] and Wc_loop [in, out] as the layer stores them, bias [H] (may be NULL) -> dWc [R + 1, H, H], db [H] (may be NULL),
+ * dW1 [H, H], db1 [H] (may be NULL), all bf16 with ONE rounding each.  M is never rounded: the products of its fp32 values with the
+ * bf16 weights (32 significant bits) are accumulated in fp64 FMA tiles, where they are exact, so an output that cancels far below its
+ * terms is still within one bf16 ulp of the exact value.  dW1's K = (R + 1) H is split over the relations; the fp64 partial products
+ * are summed in relation order: no atomics.  workspace: dn_layer_chain_wgrad_combine_workspace_bytes(R, H) (16-byte aligned). */
+size_t dn_layer_chain_wgrad_combine_workspace_bytes(int64_t R, int32_t H);
+int dn_layer_chain_wgrad_combine(const float* M, const float* c, const void* W1, const void* Wc, const void* Wc_loop, const void* bias,
+                                 int64_t R, int32_t H, void* dWc, void* db, void* dW1, void* db1, void* workspace,
+                                 size_t workspace_bytes, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
