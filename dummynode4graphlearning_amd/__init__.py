@@ -8,3 +8,15 @@ from .hipgraph import StepGraph  # noqa: F401
 from .loader import BatchLoader, PackedGraphs  # noqa: F401
 
 __version__ = "0.1.0"
+
+_GRAPH_KERNELS = ("GraphKernelData", "wl_colors", "wl_features", "wl_gram_matrices", "normalize_gram", "write_libsvm", "dataset_flags")
+
+
+def __getattr__(name):
+    # graph_kernels is also a command line (python -m dummynode4graphlearning_amd.graph_kernels): imported on first use, so that
+    # runpy does not find the module loaded before it runs it
+    if name == "graph_kernels" or name in _GRAPH_KERNELS:
+        import importlib
+        mod = importlib.import_module(".graph_kernels", __name__)
+        return mod if name == "graph_kernels" else getattr(mod, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -174,6 +174,12 @@ _SIGS = {
     "dn_hgt_attn_fwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, c_i32] + [P] * 10 + [c_f32, P, P, P]),
     "dn_hgt_attn_bwd_dst_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, c_i32] + [P] * 10 + [c_f32] + [P] * 5 + [P]),
     "dn_hgt_attn_bwd_src_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, c_i32] + [P] * 9 + [P]),
+    "dn_wl_max_entries": (c_i32, []),
+    "dn_wl_max_steps": (c_i32, []),
+    "dn_wl_gram_tile": (c_i32, []),
+    "dn_wl_refine_u64": (ctypes.c_int, [c_i64, c_i64, P, c_i32, c_i32, P, P, P, P, P, P]),
+    "dn_wl_fold_u64": (ctypes.c_int, [c_i64, c_i64, P, P, P, P, P, P]),
+    "dn_wl_gram_i64": (ctypes.c_int, [c_i64, c_i32, c_i32, P, P, P, P, P, P]),
 }
 
 _lib = None

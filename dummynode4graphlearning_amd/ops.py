@@ -4283,3 +4283,95 @@ def hgt_message_pass(q, k, v, att, msg, pri, ix, scale):
     Qp = hgt_pair_expand(q, w_att, ix)
     U = hgt_attention(Qp, k.contiguous(), v.contiguous(), pri, ix, heads, scale)
     return hgt_pair_reduce(U, w_msg, ix)
+
+
+# ------------------------------------------------------------------------------------------------ WL / WLOA graph kernels
+# (dn_wl.hip; the dataset side -- reader, node classes, features, command line -- is graph_kernels.py)
+_wl_tls = _threading.local()
+
+# The default of graph_kernels.wl_colors.  Measured by tools/graph_kernel_bench.py (docs/LAB_NOTES.md "Graph kernels: WL / WLOA"; 4096
+# NCI1-shaped graphs with dummy nodes, H = 5, fused and composed alternated in one process): 0.13 against 1.99 ms for the five
+# refinement steps, 0.27 against 2.95 ms with edge labels, spreads below 4 % -- far outside the spread, so the fused kernels are the default.
+WL_FUSED_DEFAULT = True
+
+
+def wl_fused_enabled():
+    m = getattr(_wl_tls, "fused", None)
+    return WL_FUSED_DEFAULT if m is None else m
+
+
+class wl_fused:
+    """Context manager: WL colour refinements started inside it (on this thread) sort in registers and LDS (on=True: dn_wl_refine_u64,
+    lists of up to wl_max_entries() entries; longer ones take the composed path either way) or on the composed path (on=False: a
+    device-wide segmented sort with torch ops, then dn_wl_fold_u64)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_wl_tls, "fused", None)
+        _wl_tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _wl_tls.fused = self.old
+        return False
+
+
+def wl_max_entries():
+    """The longest entry list (deg, or 2 deg with edge labels) the fused refinement sorts."""
+    return int(lib().dn_wl_max_entries())
+
+
+def wl_max_steps():
+    return int(lib().dn_wl_max_steps())
+
+
+def wl_gram_tile():
+    return int(lib().dn_wl_gram_tile())
+
+
+_WL_SIGN = -(1 << 63)          # xor with it: signed order of the int64 carriers == unsigned order of the colours
+
+
+def wl_pairing(a, b):
+    """Szudzik's pairing on int64 carriers of unsigned 64-bit values (wrapping; the comparison is unsigned)."""
+    return torch.where((a ^ _WL_SIGN) >= (b ^ _WL_SIGN), a * a + a + b, a + b * b)
+
+
+def wl_refine_fused(num_nodes, nodes, group, lds_entries, csr_ptr, nbr, edge_label, colors_in, colors_out):
+    """One launch of dn_wl_refine_u64 for the node list `nodes` (int32; None: every node)."""
+    require_gpu(nodes, csr_ptr, nbr, edge_label, colors_in, colors_out)
+    n_list = int(num_nodes) if nodes is None else int(nodes.numel())
+    check(lib().dn_wl_refine_u64(int(num_nodes), n_list, ptr(nodes), int(group), int(lds_entries), ptr(csr_ptr), ptr(nbr), ptr(edge_label),
+                                 ptr(colors_in), ptr(colors_out), stream_ptr()), "dn_wl_refine_u64")
+
+
+def wl_refine_composed(num_nodes, nodes, slots, seg, seg_ptr, nbr_long, edge_label, colors_in, colors_out):
+    """The same step without the in-kernel sort: the entries of the listed nodes (slots: their CSR slots, seg: the list position of
+    each slot's node, seg_ptr [len + 1] int64: where each node's entries start) are gathered, sorted device-wide by (node, value)
+    with two stable torch sorts, and folded by dn_wl_fold_u64.  slots / seg None: every slot in CSR order (seg must then be given as
+    the slot's node).  No read-back."""
+    require_gpu(nodes, seg, seg_ptr, nbr_long, edge_label, colors_in, colors_out)
+    n_list = int(num_nodes) if nodes is None else int(nodes.numel())
+    a = colors_in[nbr_long if slots is None else nbr_long[slots]]
+    if edge_label is not None:
+        el = edge_label if slots is None else edge_label[slots]
+        ent = torch.stack([a, wl_pairing(a, el)], 1).reshape(-1)
+        seg = seg.repeat_interleave(2)
+    else:
+        ent = a
+    key, order = torch.sort(ent ^ _WL_SIGN, stable=True)
+    by_seg = torch.sort(seg[order], stable=True)[1]
+    sorted_entries = (key[by_seg] ^ _WL_SIGN).contiguous()
+    check(lib().dn_wl_fold_u64(int(num_nodes), n_list, ptr(nodes), ptr(seg_ptr), ptr(sorted_entries) if sorted_entries.numel() else None,
+                               ptr(colors_in), ptr(colors_out), stream_ptr()), "dn_wl_fold_u64")
+
+
+def wl_gram(feat_ptr, feat_color, feat_count, feat_step, num_graphs, num_steps, use_min):
+    """[num_steps, B, B] int64: dn_wl_gram_i64 over a feature CSR (graph_kernels.wl_features)."""
+    require_gpu(feat_ptr, feat_color, feat_count, feat_step)
+    out = torch.empty((int(num_steps), int(num_graphs), int(num_graphs)), dtype=torch.int64, device=feat_ptr.device)
+    check(lib().dn_wl_gram_i64(int(num_graphs), int(num_steps), int(bool(use_min)), ptr(feat_ptr), ptr(feat_color), ptr(feat_count),
+                               ptr(feat_step), ptr(out), stream_ptr()), "dn_wl_gram_i64")
+    return out

@@ -1050,6 +1050,36 @@ int dn_layer_chain_wgrad_combine(const float* M, const float* c, const void* W1,
                                  int64_t R, int32_t H, void* dWc, void* db, void* dW1, void* db1, void* workspace,
                                  size_t workspace_bytes, dn_stream_t stream);
 
+/* ---- Weisfeiler-Lehman graph kernels at k = 1: WL and WLOA (dn_wl.hip) ----
+ * Colours are unsigned 64-bit values carried as int64 bit patterns; all arithmetic wraps mod 2^64 and every comparison is
+ * unsigned.  pairing(a, b) = a >= b ? a a + a + b : a + b b.  The graph is the deduplicated undirected CSR of a whole dataset:
+ * ptr [num_nodes + 1], nbr [ptr[num_nodes]] (global node ids), edge_label [ptr[num_nodes]] per slot or NULL.
+ *
+ * dn_wl_refine_u64: one refinement step for the nodes nodes[0 .. num_list) (NULL: every node, num_list == num_nodes).  A node's
+ * entries are colors_in[n] for every neighbour n and, with edge labels, also pairing(colors_in[n], label); colors_out[v] = the
+ * fold c = pairing(c, entry) over the ascending entries, starting from colors_in[v].  group = lanes per node: 8 or 64 (lists of at
+ * most that many entries, one per lane, sorted by a shuffle network) or 0 (one workgroup per node, lists of at most lds_entries
+ * entries -- a power of two <= dn_wl_max_entries() -- sorted in LDS).  A node whose list is longer than its launch takes is left
+ * unwritten: the caller classes the nodes (once per dataset) and sends longer lists through a device-wide segmented sort and
+ * dn_wl_fold_u64.  colors_out must not alias colors_in. */
+int32_t dn_wl_max_entries(void);
+int dn_wl_refine_u64(int64_t num_nodes, int64_t num_list, const int32_t* nodes, int32_t group, int32_t lds_entries, const int32_t* ptr,
+                     const int32_t* nbr, const int64_t* edge_label, const int64_t* colors_in, int64_t* colors_out, dn_stream_t stream);
+/* The fold alone over lists the caller has sorted: list s = sorted_entries[seg_ptr[s] .. seg_ptr[s + 1]) ascending (unsigned),
+ * colors_out[v] for v = nodes[s] (NULL: v = s).  One thread per list, any length. */
+int dn_wl_fold_u64(int64_t num_nodes, int64_t num_list, const int32_t* nodes, const int64_t* seg_ptr, const int64_t* sorted_entries,
+                   const int64_t* colors_in, int64_t* colors_out, dn_stream_t stream);
+/* All num_steps = H + 1 gram matrices in one pass from the feature CSR: row g = feat_ptr[g] .. feat_ptr[g + 1] holds graph g's
+ * distinct colours ascending (unsigned) with a count and a step (0 <= step < num_steps) each.  out [num_steps, B, B] (int64):
+ * out[h, i, j] = sum over the colours common to i and j with max(step_i, step_j) <= h of count_i count_j (use_min = 0: WL) or
+ * min(count_i, count_j) (use_min != 0: WLOA).  Every element is written (the upper triangle is computed, the lower mirrored).  A
+ * workgroup takes dn_wl_gram_tile()^2 pairs, a thread one pair: a merge join of two rows of any length, read from global memory,
+ * into num_steps <= dn_wl_max_steps() buckets in LDS.  Integer sums only: no atomics, two runs give the same bits. */
+int32_t dn_wl_max_steps(void);
+int32_t dn_wl_gram_tile(void);
+int dn_wl_gram_i64(int64_t num_graphs, int32_t num_steps, int32_t use_min, const int32_t* feat_ptr, const int64_t* feat_color,
+                   const int32_t* feat_count, const int32_t* feat_step, int64_t* out, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
