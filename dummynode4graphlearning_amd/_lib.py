@@ -180,6 +180,9 @@ _SIGS = {
     "dn_wl_refine_u64": (ctypes.c_int, [c_i64, c_i64, P, c_i32, c_i32, P, P, P, P, P, P]),
     "dn_wl_fold_u64": (ctypes.c_int, [c_i64, c_i64, P, P, P, P, P, P]),
     "dn_wl_gram_i64": (ctypes.c_int, [c_i64, c_i32, c_i32, P, P, P, P, P, P]),
+    "dn_gk_sp_lds_max_nodes": (c_i32, []),
+    "dn_gk_sp_u64": (ctypes.c_int, [c_i64, c_i64, P, c_i32, c_i32] + [P] * 9 + [c_i64, P, P, P]),
+    "dn_gk_gr_keys_u64": (ctypes.c_int, [c_i64, c_i64, c_i32] + [P] * 9 + [c_i64, P, P, P]),
 }
 
 _lib = None

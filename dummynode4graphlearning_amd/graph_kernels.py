@@ -22,7 +22,8 @@ slice is what is reproduced here: every feature entry carries the step whose sli
 Refused with ValueError (the reference handles these by accident or by undefined behaviour): a self loop (it would list the node
 twice), an `A` line that joins two graphs, edge labels wanted without an edge-label file (it dereferences end()), node labels wanted
 without a node-label file, an edge label above 2^32 - 1 (its edge-label map truncates to 32 bits), and a graph with more than
-1,000,000 / (H + 1) nodes (its MAXNUMCOLOR early stop is not built).  SP, GR and every k >= 2 generator of the tool are not built.
+1,000,000 / (H + 1) nodes (its MAXNUMCOLOR early stop is not built).  SP and GR live in graph_kernels_spgr.py (its command line takes all
+four kernels); the k >= 2 generators of the tool are not built.
 """
 import os
 import sys
@@ -310,7 +311,7 @@ def wl_gram_matrices(data, num_iterations, kernel="WL", use_node_labels=True, us
     """The H + 1 un-normalised matrices [B, B] (int64), exactly the reference's: matrix h = Phi_h Phi_h^T (WL) or the sums of
     min(Phi_h[i], Phi_h[j]) with matrix 0 all zero (WLOA).  With `features` given this is one launch and reads nothing back."""
     if kernel not in KERNELS:
-        raise ValueError("kernel %r is not built: WL and WLOA at k = 1 are (SP, GR and k >= 2 are not)" % (kernel,))
+        raise ValueError("kernel %r is not built here: WL and WLOA at k = 1 are (SP and GR: graph_kernels_spgr; k >= 2 is not)" % (kernel,))
     H = _check(data, num_iterations, use_node_labels, use_edge_labels)
     if H + 1 > ops.wl_max_steps():
         raise ValueError("num_iterations + 1 = %d exceeds the gram kernel's %d steps" % (H + 1, ops.wl_max_steps()))
@@ -363,8 +364,8 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     if args.k != 1 or args.kernel not in KERNELS:
-        ap.exit(2, "--k %d --kernel %s is not built: only --k 1 with --kernel WL or --kernel WLOA is "
-                   "(SP, GR and the k = 2 / k = 3 generators are not)\n" % (args.k, args.kernel))
+        ap.exit(2, "--k %d --kernel %s is not built here: only --k 1 with --kernel WL or --kernel WLOA is (SP and GR: "
+                   "python -m dummynode4graphlearning_amd.graph_kernels_spgr; the k = 2 / k = 3 generators are not)\n" % (args.k, args.kernel))
     jobs = []
     for name in args.datasets:
         if name not in DATASET_FLAGS:

@@ -4375,3 +4375,62 @@ def wl_gram(feat_ptr, feat_color, feat_count, feat_step, num_graphs, num_steps, 
     check(lib().dn_wl_gram_i64(int(num_graphs), int(num_steps), int(bool(use_min)), ptr(feat_ptr), ptr(feat_color), ptr(feat_count),
                                ptr(feat_step), ptr(out), stream_ptr()), "dn_wl_gram_i64")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ SP / GR graph kernels
+# (dn_gk.hip; the dataset side -- graph and centre classes, label ranks, composed paths, command line -- is graph_kernels_spgr.py)
+_gk_tls = _threading.local()
+
+# The defaults of graph_kernels_spgr.sp_features / gr_features, one per kernel.  Measured by tools/graph_kernel_spgr_bench.py
+# (docs/LAB_NOTES.md "Graph kernels: SP / GR"), fused and composed alternated in one process: 4096 NCI1-shaped graphs with dummy nodes,
+# SP 1.54 against 5.24 ms and GR 1.51 against 3.75 ms; 300 DD-shaped graphs, SP 105.1 against 110.7 ms and GR 103.1 against 161.7 ms;
+# spreads of the per-round medians below 2 % -- outside the spread everywhere, so both default to the kernels.
+GK_FUSED_DEFAULT = {"SP": True, "GR": True}
+
+
+def gk_fused_enabled(kernel=None):
+    """Whether `kernel` ("SP" or "GR") takes the dn_gk_* kernels; without a kernel: whether both do."""
+    m = getattr(_gk_tls, "fused", None)
+    if m is not None:
+        return m
+    return all(GK_FUSED_DEFAULT.values()) if kernel is None else GK_FUSED_DEFAULT[kernel]
+
+
+class gk_fused:
+    """Context manager: SP / GR feature builds started inside it (on this thread) run the dn_gk_* kernels (on=True; SP graphs above
+    gk_sp_lds_max_nodes() nodes take the composed path either way) or the composed torch-op path (on=False)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_gk_tls, "fused", None)
+        _gk_tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _gk_tls.fused = self.old
+        return False
+
+
+def gk_sp_lds_max_nodes():
+    """The largest graph whose adjacency bit matrix the fused SP kernel holds in LDS."""
+    return int(lib().dn_gk_sp_lds_max_nodes())
+
+
+def gk_sp(num_graphs, graphs, group, lds_nodes, node_ptr, csr_ptr, nbr, src_base, local_class, class_ptr, class_rank, counts=None,
+          offsets=None, out_key=None, out_count=None):
+    """One launch of dn_gk_sp_u64 for the graph list `graphs` (int32): the counting pass (counts) or the fill (offsets, out_*)."""
+    require_gpu(graphs, node_ptr, csr_ptr, nbr, src_base, local_class, class_ptr, class_rank, counts, offsets, out_key, out_count)
+    check(lib().dn_gk_sp_u64(int(num_graphs), int(graphs.numel()), ptr(graphs), int(group), int(lds_nodes), ptr(node_ptr), ptr(csr_ptr),
+                             ptr(nbr), ptr(src_base), ptr(local_class), ptr(class_ptr), ptr(class_rank), ptr(counts), ptr(offsets),
+                             0 if out_key is None else int(out_key.numel()), ptr(out_key), ptr(out_count), stream_ptr()), "dn_gk_sp_u64")
+
+
+def gk_gr_keys(num_nodes, group, item_node, item_row0, item_row1, item_offset, csr_ptr, nbr, node_label, edge_label, node_graph, ws_key,
+               ws_graph):
+    """One launch of dn_gk_gr_keys_u64 for one class of work items of a chunk."""
+    require_gpu(item_node, item_row0, item_row1, item_offset, csr_ptr, nbr, node_label, edge_label, node_graph, ws_key, ws_graph)
+    check(lib().dn_gk_gr_keys_u64(int(num_nodes), int(item_node.numel()), int(group), ptr(item_node), ptr(item_row0), ptr(item_row1),
+                                  ptr(item_offset), ptr(csr_ptr), ptr(nbr), ptr(node_label), ptr(edge_label), ptr(node_graph),
+                                  int(min(ws_key.numel(), ws_graph.numel())), ptr(ws_key), ptr(ws_graph), stream_ptr()), "dn_gk_gr_keys_u64")

@@ -1080,6 +1080,35 @@ int32_t dn_wl_gram_tile(void);
 int dn_wl_gram_i64(int64_t num_graphs, int32_t num_steps, int32_t use_min, const int32_t* feat_ptr, const int64_t* feat_color,
                    const int32_t* feat_count, const int32_t* feat_step, int64_t* out, dn_stream_t stream);
 
+/* ---- shortest-path and graphlet graph kernels (graph_classification/graph_kernels: `gram --kernel SP | GR`): the feature extractors.
+ * Both work on the dataset CSR of the dn_wl_* entry points and produce (graph, key, count) entries that the caller sorts into the
+ * feature CSR of dn_wl_gram_i64 (one step, use_min = 0).
+ *
+ * dn_gk_sp_u64: one BFS per source node over bit sets, for the graphs graphs[0 .. num_list).  group = 64: a wavefront per graph, a
+ * lane per source (graphs of at most 64 nodes); group = 0: a workgroup per graph with the adjacency bit matrix in LDS (graphs of at
+ * most lds_nodes <= dn_gk_sp_lds_max_nodes() nodes).  A graph larger than its launch takes is left alone.  A source a emits, for every
+ * label class c of its graph and every level d that reaches nodes of c, the entry key = ((src_base[a] + class_rank[class_ptr[g] + c])
+ * << 32) | d with their number; likewise the nodes it cannot reach at d = INT_MAX, and itself with count 2 at d = 2 (INT_MAX without a
+ * neighbour).  src_base[a] < 0: the source is filtered.  local_class[v] is v's class within its graph (0 .. class_ptr[g + 1] -
+ * class_ptr[g]).  offsets == NULL: the counting pass, counts[a] = entries of source a (untouched for filtered sources and for graphs
+ * left alone, so the caller zeroes it).  offsets != NULL: the fill, entries of a at out_key / out_count [offsets[a] ..), never at or
+ * beyond out_entries. */
+int32_t dn_gk_sp_lds_max_nodes(void);
+int dn_gk_sp_u64(int64_t num_graphs, int64_t num_list, const int32_t* graphs, int32_t group, int32_t lds_nodes, const int32_t* node_ptr,
+                 const int32_t* ptr, const int32_t* nbr, const int64_t* src_base, const int32_t* local_class, const int32_t* class_ptr,
+                 const int32_t* class_rank, int32_t* counts, const int64_t* offsets, int64_t out_entries, int64_t* out_key,
+                 int32_t* out_count, dn_stream_t stream);
+/* dn_gk_gr_keys_u64: the 3-node graphlet keys.  Item k is the centre item_node[k] with the rows item_row0[k] .. item_row1[k] of its
+ * ascending neighbour list; row i pairs neighbour i with every later neighbour j, and the item's pairs own the workspace slots
+ * item_offset[k] .. in that order.  Adjacent pair: a triangle, keyed only where the centre is its smallest node (ws_graph = -1
+ * elsewhere); else a wedge.  Keys: 2 / 3 without node labels; with them the reference's pairing folds (minimum over both directions
+ * of a wedge, sorted labels or the six-way minimum of a triangle).  group = lanes per item: 8 or 64 (items of at most that many
+ * pairs) or 0 (a workgroup per item, any length).  Nothing is written at or beyond workspace_keys. */
+int dn_gk_gr_keys_u64(int64_t num_nodes, int64_t num_items, int32_t group, const int32_t* item_node, const int32_t* item_row0,
+                      const int32_t* item_row1, const int64_t* item_offset, const int32_t* ptr, const int32_t* nbr, const int64_t* node_label,
+                      const int64_t* edge_label, const int32_t* node_graph, int64_t workspace_keys, int64_t* ws_key, int32_t* ws_graph,
+                      dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
