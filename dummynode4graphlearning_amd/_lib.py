@@ -183,6 +183,11 @@ _SIGS = {
     "dn_gk_sp_lds_max_nodes": (c_i32, []),
     "dn_gk_sp_u64": (ctypes.c_int, [c_i64, c_i64, P, c_i32, c_i32] + [P] * 9 + [c_i64, P, P, P]),
     "dn_gk_gr_keys_u64": (ctypes.c_int, [c_i64, c_i64, c_i32] + [P] * 9 + [c_i64, P, P, P]),
+    "dn_kwl_max_nodes": (c_i32, []),
+    "dn_kwl_max_entries": (c_i32, []),
+    "dn_kwl_init_u64": (ctypes.c_int, [c_i64, c_i64] + [P] * 7 + [P]),
+    "dn_kwl_local_u64": (ctypes.c_int, [c_i64, c_i64, c_i64, P, c_i32, c_i32, c_i32] + [P] * 8 + [P]),
+    "dn_kwl_global_u64": (ctypes.c_int, [c_i64, c_i64, c_i64, P, c_i32, c_i32] + [P] * 7 + [P]),
 }
 
 _lib = None

@@ -23,7 +23,7 @@ Refused with ValueError (the reference handles these by accident or by undefined
 twice), an `A` line that joins two graphs, edge labels wanted without an edge-label file (it dereferences end()), node labels wanted
 without a node-label file, an edge label above 2^32 - 1 (its edge-label map truncates to 32 bits), and a graph with more than
 1,000,000 / (H + 1) nodes (its MAXNUMCOLOR early stop is not built).  SP and GR live in graph_kernels_spgr.py (its command line takes all
-four kernels); the k >= 2 generators of the tool are not built.
+four kernels), the k = 2 kernels in graph_kernels_kwl.py (on features_of_colors below); this command line keeps refusing both.
 """
 import os
 import sys
@@ -285,8 +285,14 @@ def wl_features(data, num_iterations, use_node_labels=True, use_edge_labels=True
     iteration, turn them into the colour numbers nums[g][h] and look every sorted position up in them."""
     H = _check(data, num_iterations, use_node_labels, use_edge_labels)
     c = wl_colors(data, H, use_node_labels, use_edge_labels) if colors is None else colors
-    S, N, B, dev = H + 1, data.num_nodes, data.num_graphs, data.device
-    g = data.node_graph.repeat(S)
+    return features_of_colors(data.node_graph, c, data.num_graphs)
+
+
+def features_of_colors(item_graph, c, num_graphs):
+    """The feature CSR of coloured items of any kind: item_graph [N] int64 (the graph of every item, ascending), c [S, N] the colour
+    of every item after every iteration.  (The items are nodes at k = 1 and node pairs at k = 2: graph_kernels_kwl.py.)"""
+    S, N, B, dev = int(c.shape[0]), int(c.shape[1]), int(num_graphs), c.device
+    g = item_graph.repeat(S)
     it = torch.arange(S, device=dev).repeat_interleave(N)
     key, o1 = torch.sort(c.reshape(-1) ^ ops._WL_SIGN, stable=True)
     g2, o2 = torch.sort(g[o1], stable=True)                                  # now ordered by (graph, colour)

@@ -4434,3 +4434,98 @@ def gk_gr_keys(num_nodes, group, item_node, item_row0, item_row1, item_offset, c
     check(lib().dn_gk_gr_keys_u64(int(num_nodes), int(item_node.numel()), int(group), ptr(item_node), ptr(item_row0), ptr(item_row1),
                                   ptr(item_offset), ptr(csr_ptr), ptr(nbr), ptr(node_label), ptr(edge_label), ptr(node_graph),
                                   int(min(ws_key.numel(), ws_graph.numel())), ptr(ws_key), ptr(ws_graph), stream_ptr()), "dn_gk_gr_keys_u64")
+
+
+# ------------------------------------------------------------------------------------------------ 2-WL graph kernels
+# (dn_kwl.hip; the dataset side -- tuples, classes, composed path, features, command line -- is graph_kernels_kwl.py)
+_kwl_tls = _threading.local()
+
+# The default of graph_kernels_kwl.kwl_colors.  Measured by tools/graph_kernel_kwl_bench.py (docs/LAB_NOTES.md "Graph kernels: 2-WL"),
+# fused and composed alternated in one process, initial colours + 3 steps: 512 NCI1-shaped graphs with dummy nodes, WL 0.93 against
+# 94.5 ms, DWL 2.29 / 99.0, LWL 0.44 / 11.9, LWLC 0.23 / 5.7; 128 PROTEINS-shaped graphs (one above 128 nodes, composed either way), WL
+# 19.0 / 79.4, DWL 25.8 / 83.2, LWL 0.44 / 8.4, LWLC 0.28 / 4.2; spreads of the per-round medians below 4 % -- far outside the spread on
+# both shapes, so the fused kernels are the default.
+KWL_FUSED_DEFAULT = True
+
+
+def kwl_fused_enabled():
+    m = getattr(_kwl_tls, "fused", None)
+    return KWL_FUSED_DEFAULT if m is None else m
+
+
+class kwl_fused:
+    """Context manager: 2-WL refinements started inside it (on this thread) run the dn_kwl_* kernels (on=True; graphs above
+    kwl_max_nodes() nodes (WL / DWL) or with a degree above kwl_max_entries() (LWL / LWLC) take the composed path either way) or the
+    composed path (on=False: torch device ops, a device-wide segmented sort and dn_wl_fold_u64)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_kwl_tls, "fused", None)
+        _kwl_tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _kwl_tls.fused = self.old
+        return False
+
+
+def kwl_max_nodes():
+    """The largest graph whose colour matrix the fused WL / DWL step holds in LDS."""
+    return int(lib().dn_kwl_max_nodes())
+
+
+def kwl_max_entries():
+    """The longest list (a node degree) the fused LWL / LWLC step sorts."""
+    return int(lib().dn_kwl_max_entries())
+
+
+def kwl_init(num_nodes, tup_v, tup_w, csr_ptr, nbr, node_label, edge_label, colors_out):
+    """One launch of dn_kwl_init_u64: the initial colours of every tuple."""
+    require_gpu(tup_v, tup_w, csr_ptr, nbr, node_label, edge_label, colors_out)
+    check(lib().dn_kwl_init_u64(int(num_nodes), int(tup_v.numel()), ptr(tup_v), ptr(tup_w), ptr(csr_ptr), ptr(nbr), ptr(node_label),
+                                ptr(edge_label), ptr(colors_out), stream_ptr()), "dn_kwl_init_u64")
+
+
+def kwl_local(num_nodes, tuples, group, lds_entries, connected, tup_v, tup_w, row_ptr, node_first, csr_ptr, nbr, colors_in, colors_out):
+    """One launch of dn_kwl_local_u64 (LWL / LWLC) for the tuple list `tuples` (int32; None: every tuple)."""
+    require_gpu(tuples, tup_v, tup_w, row_ptr, node_first, csr_ptr, nbr, colors_in, colors_out)
+    T = int(tup_v.numel())
+    check(lib().dn_kwl_local_u64(int(num_nodes), T, T if tuples is None else int(tuples.numel()), ptr(tuples), int(group), int(lds_entries),
+                                 int(bool(connected)), ptr(tup_v), ptr(tup_w), ptr(row_ptr), ptr(node_first), ptr(csr_ptr), ptr(nbr),
+                                 ptr(colors_in), ptr(colors_out), stream_ptr()), "dn_kwl_local_u64")
+
+
+def kwl_global(num_graphs, graphs, lds_nodes, malkin, node_ptr, tuple_ptr, csr_ptr, nbr, colors_in, colors_out, work):
+    """One launch of dn_kwl_global_u64 (WL / DWL) for the graph list `graphs` (int32)."""
+    require_gpu(graphs, node_ptr, tuple_ptr, csr_ptr, nbr, colors_in, colors_out, work)
+    check(lib().dn_kwl_global_u64(int(num_graphs), int(colors_in.numel()), int(graphs.numel()), ptr(graphs), int(lds_nodes), int(bool(malkin)),
+                                  ptr(node_ptr), ptr(tuple_ptr), ptr(csr_ptr), ptr(nbr), ptr(colors_in), ptr(colors_out), ptr(work),
+                                  stream_ptr()), "dn_kwl_global_u64")
+
+
+def kwl_fold_from_max(seg, key, num_segments):
+    """The folds of the multisets (seg [E] int64 in 0 .. num_segments, key [E] int64 colour carriers; segment num_segments collects
+    what is dropped): every segment sorted ascending (unsigned), started from its maximum and folded over the rest by dn_wl_fold_u64.
+    Returns (fold [num_segments], size [num_segments]); the fold of an empty segment means nothing.  No read-back: the maxima are
+    taken out of the sorted array by a scatter to compacted positions."""
+    require_gpu(seg, key)
+    S, E, dev = int(num_segments), int(key.numel()), key.device
+    k1, order = torch.sort(key ^ _WL_SIGN, stable=True)
+    seg2, by_seg = torch.sort(seg[order], stable=True)
+    sorted_key = k1[by_seg] ^ _WL_SIGN
+    end = torch.searchsorted(seg2, torch.arange(1, S + 1, device=dev))     # (bincount would read its maximum back)
+    size = end - torch.cat([end.new_zeros(1), end[:-1]])
+    some = size > 0
+    top = sorted_key[(end - 1).clamp_(min=0)].contiguous()                  # the maximum of every non-empty segment
+    keep = torch.ones(E + 1, dtype=torch.bool, device=dev)
+    keep.scatter_(0, torch.where(some, end - 1, torch.full_like(end, E)), False)      # (slot E: nobody's; a scalar index_put would sync)
+    keep = keep[:E]
+    dest = torch.where(keep, torch.cumsum(keep, 0) - 1, torch.full((E,), E, dtype=torch.int64, device=dev))
+    rest = torch.empty(E + 1, dtype=torch.int64, device=dev)
+    rest[dest] = sorted_key
+    seg_ptr = torch.cat([end.new_zeros(1), end - torch.cumsum(some, 0)]).contiguous()
+    fold = torch.empty(S, dtype=torch.int64, device=dev)
+    check(lib().dn_wl_fold_u64(S, S, None, ptr(seg_ptr), ptr(rest), ptr(top), ptr(fold), stream_ptr()), "dn_wl_fold_u64")
+    return fold, size

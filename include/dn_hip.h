@@ -1109,6 +1109,39 @@ int dn_gk_gr_keys_u64(int64_t num_nodes, int64_t num_items, int32_t group, const
                       const int64_t* edge_label, const int32_t* node_graph, int64_t workspace_keys, int64_t* ws_key, int32_t* ws_graph,
                       dn_stream_t stream);
 
+/* ---- Weisfeiler-Lehman graph kernels at k = 2: WL, DWL, LWL and LWLC (dn_kwl.hip) ----
+ * The items are the node pairs ("tuples") of every graph of the dataset CSR of the dn_wl_* entry points: tuple t = (tup_v[t],
+ * tup_w[t]) (global node ids of one graph), graph after graph, rows in node order, a row's tuples by ascending second component.
+ * WL, DWL and LWL have all n^2 pairs of a graph; LWLC ("connected") only (i, j) with i == j or j adjacent to i.  C[a, b] is the colour
+ * of tuple (a, b) in colors_in.  A multiset is folded as: sort ascending (unsigned), start from the maximum, pairing(acc, x) over
+ * the rest in ascending order.  Every neighbour colour enters its multiset TWICE.  The new colour is the tuple's own colour folded
+ * over its local folds in ascending order, then over its global folds in ascending order; a tuple without any keeps its colour.
+ *
+ * dn_kwl_init_u64: colors_out[t] = pairing(pairing(ci, cj), c) with ci = pairing(node_label[v] + 1, 1) (1 without labels), cj =
+ * pairing(node_label[w] + 1, 2) (2 without), c = 3 or pairing(3, edge_label[slot of w in v's list]) for adjacent v, w, 1 for v == w,
+ * else 2. */
+int dn_kwl_init_u64(int64_t num_nodes, int64_t num_tuples, const int32_t* tup_v, const int32_t* tup_w, const int32_t* ptr, const int32_t* nbr,
+                    const int64_t* node_label, const int64_t* edge_label, int64_t* colors_out, dn_stream_t stream);
+/* dn_kwl_local_u64: one LWL (connected = 0) or LWLC (connected != 0) step for the tuples tuples[0 .. num_list) (NULL: every tuple).
+ * Local multiset 1 = C[x, w] for x adjacent to v, local multiset 2 = C[v, x] for x adjacent to w; LWLC keeps the x for which that
+ * pair is a tuple.  row_ptr[a] = index of the first tuple of row a, node_first[a] = first node of a's graph.  group = lanes per tuple:
+ * 8 or 64 (both degrees at most that) or 0 (one workgroup per tuple, both degrees at most lds_entries, a power of two <=
+ * dn_kwl_max_entries()).  A tuple with a longer list than its launch takes is left unwritten. */
+int32_t dn_kwl_max_entries(void);
+int dn_kwl_local_u64(int64_t num_nodes, int64_t num_tuples, int64_t num_list, const int32_t* tuples, int32_t group, int32_t lds_entries,
+                     int32_t connected, const int32_t* tup_v, const int32_t* tup_w, const int32_t* row_ptr, const int32_t* node_first,
+                     const int32_t* ptr, const int32_t* nbr, const int64_t* colors_in, int64_t* colors_out, dn_stream_t stream);
+/* dn_kwl_global_u64: one WL (malkin = 0) or DWL (malkin != 0) step for the graphs graphs[0 .. num_list), a workgroup per graph with
+ * its colour matrix in LDS: graphs of at most lds_nodes nodes (a power of two <= dn_kwl_max_nodes()); a larger one is left unwritten.
+ * Multiset 1 = C[x, w] for every x != v and the tuple's own colour FOUR times, multiset 2 = C[v, x] for every x != w.  WL: both are
+ * local.  DWL: x goes to the local multiset where it is adjacent to the exchanged node (v for 1, w for 2), else to the global one, and
+ * the four own copies to global 1.  tuple_ptr [num_graphs + 1]: first tuple of every graph (n^2 each).  work: scratch of num_tuples
+ * values (2 num_tuples for DWL), aliasing neither colour array. */
+int32_t dn_kwl_max_nodes(void);
+int dn_kwl_global_u64(int64_t num_graphs, int64_t num_tuples, int64_t num_list, const int32_t* graphs, int32_t lds_nodes, int32_t malkin,
+                      const int32_t* node_ptr, const int32_t* tuple_ptr, const int32_t* ptr, const int32_t* nbr, const int64_t* colors_in,
+                      int64_t* colors_out, int64_t* work, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
