@@ -12,6 +12,7 @@ __version__ = "0.1.0"
 _GRAPH_KERNELS = ("GraphKernelData", "wl_colors", "wl_features", "wl_gram_matrices", "normalize_gram", "write_libsvm", "dataset_flags")
 _GRAPH_KERNELS_SPGR = ("sp_features", "gr_features", "sp_gram_matrix", "gr_gram_matrix")
 _GRAPH_KERNELS_KWL = ("kwl_colors", "kwl_features", "kwl_gram_matrices")
+_GRAPH_KERNELS_K3WL = ("k3wl_colors", "k3wl_features", "k3wl_gram_matrices")
 
 
 def __getattr__(name):
@@ -29,4 +30,8 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(".graph_kernels_kwl", __name__)
         return mod if name == "graph_kernels_kwl" else getattr(mod, name)
+    if name == "graph_kernels_k3wl" or name in _GRAPH_KERNELS_K3WL:                # (a command line too)
+        import importlib
+        mod = importlib.import_module(".graph_kernels_k3wl", __name__)
+        return mod if name == "graph_kernels_k3wl" else getattr(mod, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -188,6 +188,12 @@ _SIGS = {
     "dn_kwl_init_u64": (ctypes.c_int, [c_i64, c_i64] + [P] * 7 + [P]),
     "dn_kwl_local_u64": (ctypes.c_int, [c_i64, c_i64, c_i64, P, c_i32, c_i32, c_i32] + [P] * 8 + [P]),
     "dn_kwl_global_u64": (ctypes.c_int, [c_i64, c_i64, c_i64, P, c_i32, c_i32] + [P] * 7 + [P]),
+    "dn_k3wl_max_nodes": (c_i32, []),
+    "dn_k3wl_max_entries": (c_i32, []),
+    "dn_k3wl_init_u64": (ctypes.c_int, [c_i64, c_i64, c_i32] + [P] * 7 + [P]),
+    "dn_k3wl_local_u64": (ctypes.c_int, [c_i64, c_i64, c_i64, P, c_i32, c_i32, c_i32] + [P] * 12 + [P]),
+    "dn_k3wl_global_u64": (ctypes.c_int, [c_i64, c_i64, c_i64, P, P, c_i64, c_i32, c_i32] + [P] * 5 + [P]),
+    "dn_k3wl_close_u64": (ctypes.c_int, [c_i64, c_i64, c_i32] + [P] * 9 + [P]),
 }
 
 _lib = None

@@ -4529,3 +4529,84 @@ def kwl_fold_from_max(seg, key, num_segments):
     fold = torch.empty(S, dtype=torch.int64, device=dev)
     check(lib().dn_wl_fold_u64(S, S, None, ptr(seg_ptr), ptr(rest), ptr(top), ptr(fold), stream_ptr()), "dn_wl_fold_u64")
     return fold, size
+
+
+# ------------------------------------------------------------------------------------------------ 3-WL graph kernels
+# (dn_k3wl.hip; the dataset side -- items, classes, composed path, features, command line -- is graph_kernels_k3wl.py)
+_k3wl_tls = _threading.local()
+
+# The default of graph_kernels_k3wl.k3wl_colors, one per kernel.  Measured by tools/graph_kernel_k3wl_bench.py (docs/LAB_NOTES.md
+# "Graph kernels: 3-WL"), fused and composed alternated in one process, initial colours + 2 steps: 188 MUTAG-shaped graphs with dummy
+# nodes, WL 0.84 against 222.7 ms, DWL 0.85 / 234.4, LWL 1.60 / 40.8, LWLC 1.05 / 12.1; 16 graphs of about 40 nodes, WL 0.94 / 230.8,
+# DWL 0.95 / 241.8, LWL 0.88 / 25.8, LWLC 0.45 / 7.9; spreads of the per-round medians below 6 % -- far outside the spread for every
+# kernel on both shapes, so all four default to the kernels.
+K3WL_FUSED_DEFAULT = {"WL": True, "DWL": True, "LWL": True, "LWLC": True}
+
+
+def k3wl_fused_enabled(kernel=None):
+    """Whether `kernel` ("WL", "DWL", "LWL" or "LWLC") takes the dn_k3wl_* kernels; without a kernel: whether all four do."""
+    m = getattr(_k3wl_tls, "fused", None)
+    if m is not None:
+        return m
+    return all(K3WL_FUSED_DEFAULT.values()) if kernel is None else K3WL_FUSED_DEFAULT[kernel]
+
+
+class k3wl_fused:
+    """Context manager: 3-WL refinements started inside it (on this thread) run the dn_k3wl_* kernels (on=True; graphs above
+    k3wl_max_nodes() nodes (WL / DWL) or with a degree above k3wl_max_entries() (LWL / LWLC) take the composed path either way) or the
+    composed path (on=False: torch device ops, a device-wide segmented sort and dn_wl_fold_u64)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_k3wl_tls, "fused", None)
+        _k3wl_tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _k3wl_tls.fused = self.old
+        return False
+
+
+def k3wl_max_nodes():
+    """The largest graph whose fibres the fused WL / DWL step sorts in one wavefront."""
+    return int(lib().dn_k3wl_max_nodes())
+
+
+def k3wl_max_entries():
+    """The largest degree of a graph the fused LWL / LWLC step takes (LWLC's merged list holds up to twice as many entries)."""
+    return int(lib().dn_k3wl_max_entries())
+
+
+def k3wl_init(num_nodes, connected, tup_v, tup_w, tup_u, csr_ptr, nbr, node_label, colors_out):
+    """One launch of dn_k3wl_init_u64: the initial colours of every item."""
+    require_gpu(tup_v, tup_w, tup_u, csr_ptr, nbr, node_label, colors_out)
+    check(lib().dn_k3wl_init_u64(int(num_nodes), int(tup_v.numel()), int(bool(connected)), ptr(tup_v), ptr(tup_w), ptr(tup_u), ptr(csr_ptr),
+                                 ptr(nbr), ptr(node_label), ptr(colors_out), stream_ptr()), "dn_k3wl_init_u64")
+
+
+def k3wl_local(num_nodes, items, group, lds_entries, connected, tup_v, tup_w, tup_u, node_graph, node_ptr, tuple_ptr, csr_ptr, nbr, item_key,
+               item_slot, colors_in, colors_out):
+    """One launch of dn_k3wl_local_u64 (LWL / LWLC) for the item list `items` (int32; None: every item)."""
+    require_gpu(items, tup_v, tup_w, tup_u, node_graph, node_ptr, tuple_ptr, csr_ptr, nbr, item_key, item_slot, colors_in, colors_out)
+    T = int(tup_v.numel())
+    check(lib().dn_k3wl_local_u64(int(num_nodes), T, T if items is None else int(items.numel()), ptr(items), int(group), int(lds_entries),
+                                  int(bool(connected)), ptr(tup_v), ptr(tup_w), ptr(tup_u), ptr(node_graph), ptr(node_ptr), ptr(tuple_ptr),
+                                  ptr(csr_ptr), ptr(nbr), ptr(item_key), ptr(item_slot), ptr(colors_in), ptr(colors_out), stream_ptr()),
+          "dn_k3wl_local_u64")
+
+
+def k3wl_global(num_graphs, graphs, fib_ptr, num_fibres, group, malkin, node_ptr, tuple_ptr, adj_bits, colors_in, work):
+    """One launch of dn_k3wl_global_u64 (the fibre pass of WL / DWL) for the graph list `graphs` (int32)."""
+    require_gpu(graphs, fib_ptr, node_ptr, tuple_ptr, adj_bits, colors_in, work)
+    check(lib().dn_k3wl_global_u64(int(num_graphs), int(colors_in.numel()), int(graphs.numel()), ptr(graphs), ptr(fib_ptr), int(num_fibres),
+                                   int(group), int(bool(malkin)), ptr(node_ptr), ptr(tuple_ptr), ptr(adj_bits), ptr(colors_in), ptr(work),
+                                   stream_ptr()), "dn_k3wl_global_u64")
+
+
+def k3wl_close(num_nodes, malkin, tup_v, tup_w, tup_u, node_graph, node_ptr, csr_ptr, colors_in, work, colors_out):
+    """One launch of dn_k3wl_close_u64 (the closing pass of WL / DWL) over every item."""
+    require_gpu(tup_v, tup_w, tup_u, node_graph, node_ptr, csr_ptr, colors_in, work, colors_out)
+    check(lib().dn_k3wl_close_u64(int(num_nodes), int(tup_v.numel()), int(bool(malkin)), ptr(tup_v), ptr(tup_w), ptr(tup_u), ptr(node_graph),
+                                  ptr(node_ptr), ptr(csr_ptr), ptr(colors_in), ptr(work), ptr(colors_out), stream_ptr()), "dn_k3wl_close_u64")

@@ -1142,6 +1142,47 @@ int dn_kwl_global_u64(int64_t num_graphs, int64_t num_tuples, int64_t num_list, 
                       const int32_t* node_ptr, const int32_t* tuple_ptr, const int32_t* ptr, const int32_t* nbr, const int64_t* colors_in,
                       int64_t* colors_out, int64_t* work, dn_stream_t stream);
 
+/* ---- Weisfeiler-Lehman graph kernels at k = 3: WL, DWL, LWL and LWLC (dn_k3wl.hip) ----
+ * The items are node triples of every graph of the same dataset CSR: item t = (tup_v[t], tup_w[t], tup_u[t]) (global node ids of one
+ * graph), graph after graph; tuple_ptr [num_graphs + 1]: first item of every graph.  WL, DWL and LWL have all n^3 triples of a graph,
+ * row-major.  LWLC ("connected") has (i, i, i), then (i, i, j) for adjacent i, j, then pairwise distinct (i, j, k) with at least two
+ * adjacent pairs; its items are found through item_key (per graph ascending keys (i n + j) n + k of local node numbers) and item_slot
+ * (the item of every key).  C[a, b, c] is the colour of item (a, b, c) in colors_in.  Multisets, folds and the final combination are
+ * those of k = 2: every neighbour colour enters TWICE, local folds ascending, then global folds ascending.
+ *
+ * dn_k3wl_init_u64: colors_out[t] = pairing(pairing(pairing(a, b), c), pairing(pairing(ci, cj), ck)); ci = pairing(node_label[v] + 1,
+ * 1), cj = pairing(node_label[w] + 1, 2), ck = pairing(node_label[u] + 1, 3) (1, 2, 3 without labels); a, b, c code the pairs (v, w),
+ * (v, u), (w, u): 1 adjacent, 2 not; connected: 3 adjacent, 1 the same node, 2 neither.  There are no edge labels at k = 3. */
+int dn_k3wl_init_u64(int64_t num_nodes, int64_t num_items, int32_t connected, const int32_t* tup_v, const int32_t* tup_w,
+                     const int32_t* tup_u, const int32_t* ptr, const int32_t* nbr, const int64_t* node_label, int64_t* colors_out,
+                     dn_stream_t stream);
+/* dn_k3wl_local_u64: one LWL (connected = 0) or LWLC (connected != 0) step for the items items[0 .. num_list) (NULL: every item).
+ * LWL: three local multisets, C[x, w, u] for x adjacent to v, C[v, x, u] for x adjacent to w, C[v, w, x] for x adjacent to u.  LWLC:
+ * the same entries where that triple is an item, the first two exchanges in ONE multiset, the third in another (item_key / item_slot
+ * may be NULL for LWL).  node_graph[a] = graph of node a.  group = lanes per item: 8 or 64 (every list at most that long) or 0 (one
+ * workgroup per item, every list at most lds_entries, a power of two <= 2 dn_k3wl_max_entries(): LWLC's merged list of a graph whose
+ * largest degree is dn_k3wl_max_entries()).  An item with a longer list than its launch takes is left unwritten. */
+int32_t dn_k3wl_max_entries(void);
+int dn_k3wl_local_u64(int64_t num_nodes, int64_t num_items, int64_t num_list, const int32_t* items, int32_t group, int32_t lds_entries,
+                      int32_t connected, const int32_t* tup_v, const int32_t* tup_w, const int32_t* tup_u, const int32_t* node_graph,
+                      const int32_t* node_ptr, const int32_t* tuple_ptr, const int32_t* ptr, const int32_t* nbr, const int64_t* item_key,
+                      const int32_t* item_slot, const int64_t* colors_in, int64_t* colors_out, dn_stream_t stream);
+/* dn_k3wl_global_u64: the fibre pass of one WL (malkin = 0) or DWL (malkin != 0) step for the graphs graphs[0 .. num_list) of at most
+ * `group` (8, 16, 32 or 64 <= dn_k3wl_max_nodes()) nodes, `group` lanes per fibre; fib_ptr [num_list + 1]: the first fibre of every
+ * listed graph (3 n^2 each), num_fibres = fib_ptr[num_list].  Multiset 1 = C[x, w, u] for every x != v and the triple's own colour SIX
+ * times, multiset 2 = C[v, x, u] for x != w, multiset 3 = C[v, w, x] for x != u.  WL: all local.  DWL: x is local where it is adjacent
+ * to the exchanged node (bit x - first of adj_bits[that node], first = first node of the graph), else global; the own copies are
+ * global.  work[(3 c + axis) num_items + t] receives the fold of class c (0 local, 1 global) of exchange axis + 1 of item t: 3
+ * num_items values, 6 num_items for DWL.  dn_k3wl_close_u64 then writes colors_out for every item of a graph of at most
+ * dn_k3wl_max_nodes() nodes from colors_in and work (which folds exist follows from the sizes and degrees). */
+int32_t dn_k3wl_max_nodes(void);
+int dn_k3wl_global_u64(int64_t num_graphs, int64_t num_items, int64_t num_list, const int32_t* graphs, const int32_t* fib_ptr,
+                       int64_t num_fibres, int32_t group, int32_t malkin, const int32_t* node_ptr, const int32_t* tuple_ptr,
+                       const int64_t* adj_bits, const int64_t* colors_in, int64_t* work, dn_stream_t stream);
+int dn_k3wl_close_u64(int64_t num_nodes, int64_t num_items, int32_t malkin, const int32_t* tup_v, const int32_t* tup_w, const int32_t* tup_u,
+                      const int32_t* node_graph, const int32_t* node_ptr, const int32_t* ptr, const int64_t* colors_in, const int64_t* work,
+                      int64_t* colors_out, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
