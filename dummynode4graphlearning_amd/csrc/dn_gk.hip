@@ -23,22 +23,14 @@
 
 #include "dn_common.h"
 #include "dn_hip.h"
+#include "dn_wl_common.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kSpLdsNodes = 512;         // the bit matrix of 512 nodes is 32 KiB; with the per-wave sets and histograms 41.8 KiB
 constexpr int kIntMax = 0x7fffffff;
-
-__device__ __forceinline__ u64 gk_pair(u64 a, u64 b) { return a >= b ? a * a + a + b : a + b * b; }
-
-__device__ __forceinline__ u64 gk_shfl64(u64 v, int src) {
-    const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src, 64), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
 
 __device__ __forceinline__ int64_t sp_key(int64_t base, int32_t rb, int32_t d) { return (int64_t)(((u64)(base + rb) << 32) | (u64)(unsigned)d); }
 
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void sp_wave_kernel(int64_t num, const int3
         if (last) break;
         u64 next = 0;
         for (int32_t j = 0; j < n; ++j) {
-            const u64 row = gk_shfl64(adj, j);
+            const u64 row = shfl64(adj, j);
             if ((frontier >> j) & 1) next |= row;
         }
         frontier = next & ~visited;
@@ -248,12 +240,12 @@ struct GrArgs {
 };
 
 // P(list) of the reference: the pairing fold over the list, started at the list's length
-__device__ __forceinline__ u64 gk_fold3(u64 a, u64 b, u64 c) { return gk_pair(gk_pair(gk_pair(3ull, a), b), c); }
-__device__ __forceinline__ u64 gk_fold5(u64 a, u64 b, u64 c, u64 d, u64 e) { return gk_pair(gk_pair(gk_pair(gk_pair(gk_pair(5ull, a), b), c), d), e); }
+__device__ __forceinline__ u64 gk_fold3(u64 a, u64 b, u64 c) { return wl_pair(wl_pair(wl_pair(3ull, a), b), c); }
+__device__ __forceinline__ u64 gk_fold5(u64 a, u64 b, u64 c, u64 d, u64 e) { return wl_pair(wl_pair(wl_pair(wl_pair(wl_pair(5ull, a), b), c), d), e); }
 __device__ __forceinline__ u64 gk_min(u64 a, u64 b) { return a < b ? a : b; }
 
 __device__ __forceinline__ u64 gk_fold6(u64 a, u64 b, u64 c, u64 d, u64 e, u64 f) {
-    return gk_pair(gk_pair(gk_pair(gk_pair(gk_pair(gk_pair(6ull, a), b), c), d), e), f);
+    return wl_pair(wl_pair(wl_pair(wl_pair(wl_pair(wl_pair(6ull, a), b), c), d), e), f);
 }
 
 // the pair (slot eu, slot ew) of centre v, eu < ew: its key and graph into workspace slot pos

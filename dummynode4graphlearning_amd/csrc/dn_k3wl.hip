@@ -25,32 +25,19 @@
 
 #include "dn_common.h"
 #include "dn_hip.h"
+#include "dn_wl_common.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kBlock = 256;
 constexpr int kMaxNodes = 64;            // the largest graph of the WL / DWL kernel (a fibre in one wavefront, an adjacency row in 64 bits)
 constexpr int kMaxEntries = 256;         // the largest degree of the LWL / LWLC workgroup kernel: lists of up to 2 kMaxEntries (LWLC's
                                          // merged one), three of them: 12 KiB of LDS
 
-__device__ __forceinline__ u64 k3_pair(u64 a, u64 b) { return a >= b ? a * a + a + b : a + b * b; }
-
-__device__ __forceinline__ u64 k3_shfl64(u64 v, int src) {
-    const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src, 64), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
-
 // is w in the ascending list nbr[ptr[v] .. ptr[v + 1])?
 __device__ __forceinline__ bool k3_adjacent(const int32_t* __restrict__ ptr, const int32_t* __restrict__ nbr, int32_t v, int32_t w) {
-    int32_t lo = ptr[v], hi = ptr[v + 1];
-    const int32_t end = hi;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (nbr[mid] < w) lo = mid + 1;
-        else hi = mid;
-    }
+    const int32_t end = ptr[v + 1];
+    const int32_t lo = wl_lower_bound(nbr, ptr[v], end, w);
     return lo < end && nbr[lo] == w;
 }
 
@@ -64,13 +51,8 @@ __device__ __forceinline__ int32_t k3_slot(bool connected, int32_t a, int32_t b,
     const int64_t key = ((int64_t)(a - first) * n + (b - first)) * n + (c - first);
     const int32_t t0 = tuple_ptr[g];
     if (!connected) return (int32_t)(t0 + key);
-    int32_t lo = t0, hi = tuple_ptr[g + 1];
-    const int32_t end = hi;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (item_key[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
+    const int32_t end = tuple_ptr[g + 1];
+    const int32_t lo = wl_lower_bound(item_key, t0, end, key);
     return lo < end && item_key[lo] == key ? item_slot[lo] : -1;
 }
 
@@ -89,9 +71,9 @@ __device__ __forceinline__ u64 k3_combine(u64 own, u64* fl, bool* hl, u64* fg, b
     k3_sort3(fg, hg);
     u64 acc = own;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) if (hl[i]) acc = k3_pair(acc, fl[i]);
+    for (int i = 0; i < 3; ++i) if (hl[i]) acc = wl_pair(acc, fl[i]);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) if (hg[i]) acc = k3_pair(acc, fg[i]);
+    for (int i = 0; i < 3; ++i) if (hg[i]) acc = wl_pair(acc, fg[i]);
     return acc;
 }
 
@@ -102,8 +84,8 @@ __global__ __launch_bounds__(kBlock) void k3_init_kernel(int64_t T, int connecte
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (t >= T) return;
     const int32_t v = tup_v[t], w = tup_w[t], u = tup_u[t];
-    const u64 ci = nl ? k3_pair(nl[v] + 1ull, 1ull) : 1ull, cj = nl ? k3_pair(nl[w] + 1ull, 2ull) : 2ull,
-              ck = nl ? k3_pair(nl[u] + 1ull, 3ull) : 3ull;
+    const u64 ci = nl ? wl_pair(nl[v] + 1ull, 1ull) : 1ull, cj = nl ? wl_pair(nl[w] + 1ull, 2ull) : 2ull,
+              ck = nl ? wl_pair(nl[u] + 1ull, 3ull) : 3ull;
     // all triples: 1 adjacent, 2 not (a repeated node is not adjacent); LWLC: 3 adjacent, 1 the same node, 2 neither -- which gives
     // (1, 1, 1) for (i, i, i) and (1, 3, 3) for (i, i, j)
     auto code = [&](int32_t a, int32_t b) -> u64 {
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void k3_init_kernel(int64_t T, int connecte
         return adj ? 3ull : a == b ? 1ull : 2ull;
     };
     const u64 a = code(v, w), b = code(v, u), c = code(w, u);
-    out[t] = k3_pair(k3_pair(k3_pair(a, b), c), k3_pair(k3_pair(ci, cj), ck));
+    out[t] = wl_pair(wl_pair(wl_pair(a, b), c), wl_pair(wl_pair(ci, cj), ck));
 }
 
 struct K3Local {
@@ -145,9 +127,8 @@ __device__ __forceinline__ bool k3_entry(const K3Local& a, int m, int32_t k, int
     return true;
 }
 
-// G lanes per triple (G = 8 or 64), one entry per lane, the three lists one after the other through the same shuffle network.
-// Padding lanes hold 2^64 - 1: a real entry of that value is indistinguishable from the padding, so the first cnt sorted values are
-// the list's sorted entries either way.
+// G lanes per triple (G = 8 or 64), one entry per lane, the three lists one after the other through the same shuffle network
+// (dn_wl_common.h: wl_sort_group and the padding, wl_fold_doubled_group).
 template <int G>
 __global__ __launch_bounds__(kBlock) void k3_local_group_kernel(int64_t num, const int32_t* __restrict__ list, K3Local a,
                                                                 const u64* __restrict__ cin, u64* __restrict__ cout) {
@@ -173,24 +154,8 @@ __global__ __launch_bounds__(kBlock) void k3_local_group_kernel(int64_t num, con
         if (!kept) val = ~0ull;
         const u64 ballot = __ballot(kept);
         const int cnt = G == 64 ? __popcll(ballot) : __popcll((ballot >> base) & ((1ull << (G & 63)) - 1ull));
-#pragma unroll
-        for (int k = 2; k <= G; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                const u64 o = k3_shfl64(val, lane ^ j);
-                const bool keep_min = ((l & k) == 0) == ((l & j) == 0);
-                const u64 mn = val < o ? val : o, mx = val < o ? o : val;
-                val = keep_min ? mn : mx;
-            }
-        }
-        const u64 top = k3_shfl64(val, base + (cnt > 0 ? cnt - 1 : 0));
-        u64 acc = top;
-        for (int i = 0; i < G - 1; ++i) {
-            if (G == 64 && i >= cnt - 1) break;                  // (one triple per wavefront: cnt is uniform)
-            const u64 e = k3_shfl64(val, base + i);
-            if (i < cnt - 1) acc = k3_pair(k3_pair(acc, e), e);
-        }
-        fold[m] = k3_pair(acc, top);                             // the maximum's second copy comes last
+        val = wl_sort_group<G>(val, lane, l);
+        fold[m] = wl_fold_doubled_group<G>(val, base, cnt);
         has[m] = cnt > 0;
     }
     if (active && l == 0) cout[t] = k3_combine(cin[t], fold, has, none, no);
@@ -224,27 +189,11 @@ __global__ __launch_bounds__(kBlock) void k3_local_block_kernel(const int32_t* _
         }
         if (mine) atomicAdd(&kept_s[m], mine);                   // a count, whatever the order of the additions
         __syncthreads();
-        for (int32_t k = 2; k <= n2; k <<= 1) {
-            for (int32_t j = k >> 1; j > 0; j >>= 1) {
-                for (int32_t p = tid; p < (n2 >> 1); p += kBlock) {
-                    const int32_t lo = ((p & ~(j - 1)) << 1) | (p & (j - 1)), hi = lo + j;
-                    const u64 x = s[lo], y = s[hi];
-                    if ((x > y) == ((lo & k) == 0)) { s[lo] = y; s[hi] = x; }
-                }
-                __syncthreads();
-            }
-        }
+        wl_sort_block<kBlock>(s, n2, tid);
     }
     if (tid == 0 || tid == 64 || tid == 128) {                   // one lane of three wavefronts: a list each
         const int m = tid >> 6;
-        const u64* s = k3_s + (size_t)m * cap;
-        const int cnt = kept_s[m];
-        if (cnt > 0) {
-            const u64 top = s[cnt - 1];
-            u64 acc = top;
-            for (int i = 0; i < cnt - 1; ++i) acc = k3_pair(k3_pair(acc, s[i]), s[i]);
-            fold_s[m] = k3_pair(acc, top);
-        }
+        if (kept_s[m] > 0) fold_s[m] = wl_fold_doubled_block(k3_s + (size_t)m * cap, kept_s[m]);
     }
     __syncthreads();
     if (tid == 0) {
@@ -300,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void k3_fibre_kernel(int64_t num_fibres, in
     for (int k = 2; k <= G; k <<= 1) {
 #pragma unroll
         for (int j = k >> 1; j > 0; j >>= 1) {
-            const u64 o = k3_shfl64(key, lane ^ j);
+            const u64 o = shfl64(key, lane ^ j);
             const int os = __shfl(src, lane ^ j, 64);
             const bool keep_min = ((l & k) == 0) == ((l & j) == 0);
             const bool less = key < o || (key == o && src < os);
@@ -322,11 +271,11 @@ __global__ __launch_bounds__(kBlock) void k3_fibre_kernel(int64_t num_fibres, in
         if (glob) m_glo = i;
         else m_loc = i;
     }
-    const u64 top_loc = k3_shfl64(key, base + (m_loc >= 0 ? m_loc : 0)), top_glo = k3_shfl64(key, base + (m_glo >= 0 ? m_glo : 0));
+    const u64 top_loc = shfl64(key, base + (m_loc >= 0 ? m_loc : 0)), top_glo = shfl64(key, base + (m_glo >= 0 ? m_glo : 0));
     u64 a_loc = top_loc, a_glo = top_glo;
     for (int i = 0; i < G; ++i) {
         const int s = __shfl(src, base + i, 64);
-        const u64 e = k3_shfl64(key, base + i);
+        const u64 e = shfl64(key, base + i);
         if (!mine || i >= n) continue;
         const bool self = s == l;
         if (self && axis != 0) continue;
@@ -334,7 +283,7 @@ __global__ __launch_bounds__(kBlock) void k3_fibre_kernel(int64_t num_fibres, in
         int copies = self ? 6 : 2;
         if (i == (glob ? m_glo : m_loc)) --copies;               // one copy of the class's maximum started the fold
         u64 acc = glob ? a_glo : a_loc;
-        for (int c = 0; c < copies; ++c) acc = k3_pair(acc, e);
+        for (int c = 0; c < copies; ++c) acc = wl_pair(acc, e);
         if (glob) a_glo = acc;
         else a_loc = acc;
     }

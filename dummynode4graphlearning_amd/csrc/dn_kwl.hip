@@ -24,32 +24,13 @@
 
 #include "dn_common.h"
 #include "dn_hip.h"
+#include "dn_wl_common.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kBlock = 256;
 constexpr int kMaxNodes = 128;           // the largest graph of the WL / DWL kernel (its colour matrix and source indices in LDS)
 constexpr int kMaxEntries = 1024;        // the longest list (a degree) of the LWL / LWLC workgroup kernel: 2 lists, 16 KiB of LDS
-
-__device__ __forceinline__ u64 kwl_pair(u64 a, u64 b) { return a >= b ? a * a + a + b : a + b * b; }
-
-__device__ __forceinline__ u64 kwl_shfl64(u64 v, int src) {
-    const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src, 64), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
-
-// first slot of the ascending list nbr[beg .. end) that holds a value >= w
-__device__ __forceinline__ int32_t kwl_lower(const int32_t* __restrict__ nbr, int32_t beg, int32_t end, int32_t w) {
-    int32_t lo = beg, hi = end;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (nbr[mid] < w) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // index of tuple (a, b) in the colour array, -1 where it is no tuple (LWLC only).  row_ptr[a] is the first tuple of row a: all
 // pairs: tuples of the earlier graphs + (a - first) n, connected: ptr[a] + a (a row holds a itself among its ascending neighbours)
@@ -58,7 +39,7 @@ __device__ __forceinline__ int32_t kwl_tuple(bool connected, int32_t a, int32_t 
                                              const int32_t* __restrict__ nbr) {
     if (!connected) return row_ptr[a] + (b - node_first[a]);
     const int32_t beg = ptr[a], end = ptr[a + 1];
-    const int32_t p = kwl_lower(nbr, beg, end, b);
+    const int32_t p = wl_lower_bound(nbr, beg, end, b);
     if (a == b) return row_ptr[a] + (p - beg);
     if (p < end && nbr[p] == b) return row_ptr[a] + (p - beg) + (b > a ? 1 : 0);
     return -1;
@@ -69,10 +50,10 @@ __device__ __forceinline__ u64 kwl_combine(u64 own, u64 l1, bool hl1, u64 l2, bo
     if (hl1 && hl2 && l1 > l2) { const u64 t = l1; l1 = l2; l2 = t; }
     if (hg1 && hg2 && g1 > g2) { const u64 t = g1; g1 = g2; g2 = t; }
     u64 acc = own;
-    if (hl1) acc = kwl_pair(acc, l1);
-    if (hl2) acc = kwl_pair(acc, l2);
-    if (hg1) acc = kwl_pair(acc, g1);
-    if (hg2) acc = kwl_pair(acc, g2);
+    if (hl1) acc = wl_pair(acc, l1);
+    if (hl2) acc = wl_pair(acc, l2);
+    if (hg1) acc = wl_pair(acc, g1);
+    if (hg2) acc = wl_pair(acc, g2);
     return acc;
 }
 
@@ -82,12 +63,12 @@ __global__ __launch_bounds__(kBlock) void kwl_init_kernel(int64_t T, const int32
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (t >= T) return;
     const int32_t v = tup_v[t], w = tup_w[t];
-    const u64 ci = nl ? kwl_pair(nl[v] + 1ull, 1ull) : 1ull, cj = nl ? kwl_pair(nl[w] + 1ull, 2ull) : 2ull;
+    const u64 ci = nl ? wl_pair(nl[v] + 1ull, 1ull) : 1ull, cj = nl ? wl_pair(nl[w] + 1ull, 2ull) : 2ull;
     const int32_t end = ptr[v + 1];
-    const int32_t p = kwl_lower(nbr, ptr[v], end, w);
+    const int32_t p = wl_lower_bound(nbr, ptr[v], end, w);
     u64 c = v == w ? 1ull : 2ull;
-    if (p < end && nbr[p] == w) c = el ? kwl_pair(3ull, el[p]) : 3ull;
-    out[t] = kwl_pair(kwl_pair(ci, cj), c);
+    if (p < end && nbr[p] == w) c = el ? wl_pair(3ull, el[p]) : 3ull;
+    out[t] = wl_pair(wl_pair(ci, cj), c);
 }
 
 // entry k of list L of tuple (v, w): L = 0: C[x, w] for x = the k-th neighbour of v; L = 1: C[v, x] for x = the k-th neighbour of w
@@ -101,9 +82,8 @@ __device__ __forceinline__ bool kwl_local_entry(int L, int32_t k, int32_t v, int
     return true;
 }
 
-// G lanes per tuple (G = 8 or 64), one entry per lane, the two lists one after the other through the same shuffle network.  Padding
-// lanes hold 2^64 - 1: a real entry of that value is indistinguishable from the padding, so the first cnt sorted values are the
-// list's sorted entries either way.
+// G lanes per tuple (G = 8 or 64), one entry per lane, the two lists one after the other through the same shuffle network
+// (dn_wl_common.h: wl_sort_group and the padding, wl_fold_doubled_group).
 template <int G>
 __global__ __launch_bounds__(kBlock) void kwl_local_group_kernel(int64_t num, const int32_t* __restrict__ list, int connected,
                                                                  const int32_t* __restrict__ tup_v, const int32_t* __restrict__ tup_w,
@@ -132,24 +112,8 @@ __global__ __launch_bounds__(kBlock) void kwl_local_group_kernel(int64_t num, co
         if (!kept) val = ~0ull;
         const u64 ballot = __ballot(kept);
         const int cnt = G == 64 ? __popcll(ballot) : __popcll((ballot >> base) & ((1ull << (G & 63)) - 1ull));
-#pragma unroll
-        for (int k = 2; k <= G; k <<= 1) {
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                const u64 o = kwl_shfl64(val, lane ^ j);
-                const bool keep_min = ((l & k) == 0) == ((l & j) == 0);
-                const u64 mn = val < o ? val : o, mx = val < o ? o : val;
-                val = keep_min ? mn : mx;
-            }
-        }
-        const u64 top = kwl_shfl64(val, base + (cnt > 0 ? cnt - 1 : 0));
-        u64 acc = top;
-        for (int i = 0; i < G - 1; ++i) {
-            if (G == 64 && i >= cnt - 1) break;                  // (one tuple per wavefront: cnt is uniform)
-            const u64 e = kwl_shfl64(val, base + i);
-            if (i < cnt - 1) acc = kwl_pair(kwl_pair(acc, e), e);
-        }
-        fold[L] = kwl_pair(acc, top);                            // the maximum's second copy comes last
+        val = wl_sort_group<G>(val, lane, l);
+        fold[L] = wl_fold_doubled_group<G>(val, base, cnt);
         has[L] = cnt > 0;
     }
     if (active && l == 0) cout[t] = kwl_combine(cin[t], fold[0], has[0], fold[1], has[1], 0ull, false, 0ull, false);
@@ -184,27 +148,11 @@ __global__ __launch_bounds__(kBlock) void kwl_local_block_kernel(const int32_t* 
         }
         if (mine) atomicAdd(&kept_s[L], mine);                   // a count, whatever the order of the additions
         __syncthreads();
-        for (int32_t k = 2; k <= n2; k <<= 1) {
-            for (int32_t j = k >> 1; j > 0; j >>= 1) {
-                for (int32_t p = tid; p < (n2 >> 1); p += kBlock) {
-                    const int32_t lo = ((p & ~(j - 1)) << 1) | (p & (j - 1)), hi = lo + j;
-                    const u64 a = s[lo], b = s[hi];
-                    if ((a > b) == ((lo & k) == 0)) { s[lo] = b; s[hi] = a; }
-                }
-                __syncthreads();
-            }
-        }
+        wl_sort_block<kBlock>(s, n2, tid);
     }
     if (tid == 0 || tid == 64) {                                 // one lane of two wavefronts: a list each
         const int L = tid >> 6;
-        const u64* s = kwl_s + (size_t)L * cap;
-        const int cnt = kept_s[L];
-        if (cnt > 0) {
-            const u64 top = s[cnt - 1];
-            u64 acc = top;
-            for (int i = 0; i < cnt - 1; ++i) acc = kwl_pair(kwl_pair(acc, s[i]), s[i]);
-            fold_s[L] = kwl_pair(acc, top);
-        }
+        if (kept_s[L] > 0) fold_s[L] = wl_fold_doubled_block(kwl_s + (size_t)L * cap, kept_s[L]);
     }
     __syncthreads();
     if (tid == 0) cout[t] = kwl_combine(cin[t], fold_s[0], kept_s[0] > 0, fold_s[1], kept_s[1] > 0, 0ull, false, 0ull, false);
@@ -264,10 +212,10 @@ __device__ __forceinline__ void kwl_walk(const u64* __restrict__ K, const uint8_
         int m = (!SKIP && s == self) ? 4 : 2;
         if (i == (g ? m_glo : m_loc)) --m;                       // one copy of the class's maximum started the fold
         u64 acc = g ? a_glo : a_loc;
-        acc = kwl_pair(acc, k);
-        if (m > 1) acc = kwl_pair(acc, k);
-        if (m > 2) acc = kwl_pair(acc, k);
-        if (m > 3) acc = kwl_pair(acc, k);
+        acc = wl_pair(acc, k);
+        if (m > 1) acc = wl_pair(acc, k);
+        if (m > 2) acc = wl_pair(acc, k);
+        if (m > 3) acc = wl_pair(acc, k);
         if (g) a_glo = acc;
         else a_loc = acc;
     }

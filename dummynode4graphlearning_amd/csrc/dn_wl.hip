@@ -21,22 +21,14 @@
 
 #include "dn_common.h"
 #include "dn_hip.h"
+#include "dn_wl_common.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kBlock = 256;
 constexpr int kMaxEntries = 8192;        // the longest list the workgroup kernel sorts (64 KiB of LDS)
 constexpr int kMaxSteps = 16;            // H + 1 of the gram kernel (2 KiB of LDS buckets per step)
 constexpr int kTile = 16;                // the gram kernel's pair tile: kTile x kTile pairs per workgroup
-
-__device__ __forceinline__ u64 wl_pair(u64 a, u64 b) { return a >= b ? a * a + a + b : a + b * b; }
-
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {
-    const unsigned lo = (unsigned)__shfl((int)(unsigned)v, src, 64), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), src, 64);
-    return ((u64)hi << 32) | lo;
-}
 
 // entry k of a node whose slots start at beg: mult = 1: c[nbr]; mult = 2: odd k = pairing(c[nbr], label), even k = c[nbr]
 __device__ __forceinline__ u64 wl_entry(int32_t beg, int32_t k, bool labelled, const int32_t* __restrict__ nbr,
@@ -46,8 +38,7 @@ __device__ __forceinline__ u64 wl_entry(int32_t beg, int32_t k, bool labelled, c
     return (labelled && (k & 1)) ? wl_pair(c, el[e]) : c;
 }
 
-// G lanes per node (G = 8 or 64), one entry per lane.  Padding lanes hold 2^64 - 1: a real entry of that value is indistinguishable
-// from the padding, so the first cnt sorted values are the node's sorted entries either way.
+// G lanes per node (G = 8 or 64), one entry per lane; padding lanes hold 2^64 - 1 (dn_wl_common.h: wl_sort_group)
 template <int G>
 __global__ __launch_bounds__(kBlock) void wl_refine_group_kernel(int64_t num, const int32_t* __restrict__ nodes,
                                                                  const int32_t* __restrict__ ptr, const int32_t* __restrict__ nbr,
@@ -68,16 +59,7 @@ __global__ __launch_bounds__(kBlock) void wl_refine_group_kernel(int64_t num, co
     }
     u64 val = ~0ull;
     if (l < cnt) val = wl_entry(beg, l, labelled, nbr, el, cin);
-#pragma unroll
-    for (int k = 2; k <= G; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const u64 o = shfl64(val, lane ^ j);
-            const bool keep_min = ((l & k) == 0) == ((l & j) == 0);
-            const u64 mn = val < o ? val : o, mx = val < o ? o : val;
-            val = keep_min ? mn : mx;
-        }
-    }
+    val = wl_sort_group<G>(val, lane, l);
     u64 c = active ? cin[v] : 0ull;
     for (int i = 0; i < G; ++i) {
         if (G == 64 && i >= cnt) break;                      // (one node per wavefront: cnt is uniform)
@@ -103,16 +85,7 @@ __global__ __launch_bounds__(kBlock) void wl_refine_block_kernel(const int32_t* 
     while (n2 < cnt) n2 <<= 1;
     for (int32_t k = tid; k < n2; k += kBlock) wl_s[k] = k < cnt ? wl_entry(beg, k, labelled, nbr, el, cin) : ~0ull;
     __syncthreads();
-    for (int32_t k = 2; k <= n2; k <<= 1) {
-        for (int32_t j = k >> 1; j > 0; j >>= 1) {
-            for (int32_t t = tid; t < (n2 >> 1); t += kBlock) {
-                const int32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo + j;
-                const u64 a = wl_s[lo], b = wl_s[hi];
-                if ((a > b) == ((lo & k) == 0)) { wl_s[lo] = b; wl_s[hi] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    wl_sort_block<kBlock>(wl_s, n2, tid);
     if (tid == 0) {
         u64 c = cin[v];
         for (int32_t i = 0; i < cnt; ++i) c = wl_pair(c, wl_s[i]);

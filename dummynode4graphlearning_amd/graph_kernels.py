@@ -357,10 +357,10 @@ def gram_file(gram_dir, dataset, kernel, h):
     return os.path.join(gram_dir, "%s__%s_%d.gram" % (dataset, "WL1" if kernel == "WL" else kernel, h))
 
 
-def main(argv=None):
+def cli_parser(module, description):
+    """The arguments of the reference's tool (gram.cpp:38-104), the same for the command line of every graph-kernel module."""
     import argparse
-    ap = argparse.ArgumentParser(prog="python -m dummynode4graphlearning_amd.graph_kernels",
-                                 description="WL / WLOA gram matrices (k = 1) in the reference's libsvm text")
+    ap = argparse.ArgumentParser(prog="python -m dummynode4graphlearning_amd." + module, description=description)
     ap.add_argument("--dataset_dir", default="./datasets")
     ap.add_argument("--gram_dir", default="./svm/GM/EXP")
     ap.add_argument("--k", type=int, default=1)
@@ -368,10 +368,13 @@ def main(argv=None):
     ap.add_argument("--n_iters", type=int, default=1)
     ap.add_argument("--datasets", nargs="*", default=[])
     ap.add_argument("--device", default="cuda")
-    args = ap.parse_args(argv)
-    if args.k != 1 or args.kernel not in KERNELS:
-        ap.exit(2, "--k %d --kernel %s is not built here: only --k 1 with --kernel WL or --kernel WLOA is (SP and GR: "
-                   "python -m dummynode4graphlearning_amd.graph_kernels_spgr; the k = 2 / k = 3 generators are not)\n" % (args.k, args.kernel))
+    return ap
+
+
+def cli_run(args, grams):
+    """What every command line does once it has accepted (--k, --kernel): read all the datasets named (an unknown name: the reference's
+    warning, then the read), then per dataset the matrices `grams(name, data, use_node_labels, use_edge_labels)` -- (file, matrix)
+    pairs -- written as libsvm text, and the reference's line with the time."""
     jobs = []
     for name in args.datasets:
         if name not in DATASET_FLAGS:
@@ -379,11 +382,26 @@ def main(argv=None):
         jobs.append((name, GraphKernelData.from_dir(args.dataset_dir, name, device=args.device)) + dataset_flags(name))
     for name, data, use_nl, use_el in jobs:
         t0 = time.time()
-        Gs = wl_gram_matrices(data, args.n_iters, args.kernel, use_nl, use_el)
-        for h, G in enumerate(Gs):
-            write_libsvm(G, data.classes, gram_file(args.gram_dir, name, args.kernel, h))
+        for path, G in grams(name, data, use_nl, use_el):
+            write_libsvm(G, data.classes, path)
         print("%s-%d\t%s\t%d seconds" % (args.kernel, args.n_iters, name, int(time.time() - t0)))
     return 0
+
+
+def cli_per_iteration(args, gram_file, matrices):
+    """cli_run's `grams` for a kernel with one matrix per iteration: matrices(data, n_iters, kernel, flags) into gram_file(.., h)."""
+    return lambda name, data, use_nl, use_el: [
+        (gram_file(args.gram_dir, name, args.kernel, h), G)
+        for h, G in enumerate(matrices(data, args.n_iters, args.kernel, use_nl, use_el))]
+
+
+def main(argv=None):
+    ap = cli_parser("graph_kernels", "WL / WLOA gram matrices (k = 1) in the reference's libsvm text")
+    args = ap.parse_args(argv)
+    if args.k != 1 or args.kernel not in KERNELS:
+        ap.exit(2, "--k %d --kernel %s is not built here: only --k 1 with --kernel WL or --kernel WLOA is (SP and GR: "
+                   "python -m dummynode4graphlearning_amd.graph_kernels_spgr; the k = 2 / k = 3 generators are not)\n" % (args.k, args.kernel))
+    return cli_run(args, cli_per_iteration(args, gram_file, wl_gram_matrices))
 
 
 if __name__ == "__main__":

@@ -34,14 +34,13 @@ product does not fit 32 bits, for GR a key workspace smaller than one work item.
 """
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 from . import graph_kernels as gk
 from . import ops
-from .graph_kernels import GraphKernelData, WLFeatures, dataset_flags, write_libsvm
+from .graph_kernels import GraphKernelData, WLFeatures, dataset_flags, write_libsvm  # noqa: F401
 
 INT_MAX = 2147483647
 SP_MAX_NODES = 32767
@@ -388,34 +387,16 @@ def gram_file(gram_dir, dataset, kernel):
 
 
 def main(argv=None):
-    import argparse
     argv = sys.argv[1:] if argv is None else list(argv)
-    ap = argparse.ArgumentParser(prog="python -m dummynode4graphlearning_amd.graph_kernels_spgr",
-                                 description="SP / GR gram matrices in the reference's libsvm text (WL / WLOA: graph_kernels)")
-    ap.add_argument("--dataset_dir", default="./datasets")
-    ap.add_argument("--gram_dir", default="./svm/GM/EXP")
-    ap.add_argument("--k", type=int, default=1)
-    ap.add_argument("--kernel", default="WL")
-    ap.add_argument("--n_iters", type=int, default=1)
-    ap.add_argument("--datasets", nargs="*", default=[])
-    ap.add_argument("--device", default="cuda")
+    ap = gk.cli_parser("graph_kernels_spgr", "SP / GR gram matrices in the reference's libsvm text (WL / WLOA: graph_kernels)")
     args = ap.parse_args(argv)
     if args.kernel in gk.KERNELS:
         return gk.main(argv)
     if args.k != 1 or args.kernel not in KERNELS:
         ap.exit(2, "--k %d --kernel %s is not built: only --k 1 with --kernel SP, GR, WL or WLOA is "
                    "(the k = 2 / k = 3 generators are not)\n" % (args.k, args.kernel))
-    jobs = []
-    for name in args.datasets:
-        if name not in gk.DATASET_FLAGS:
-            print("Warning: %s is not a valid dataset." % name)
-        jobs.append((name, GraphKernelData.from_dir(args.dataset_dir, name, device=args.device)) + dataset_flags(name))
-    for name, data, use_nl, use_el in jobs:
-        t0 = time.time()
-        G = sp_gram_matrix(data, use_nl) if args.kernel == "SP" else gr_gram_matrix(data, use_nl, use_el)
-        write_libsvm(G, data.classes, gram_file(args.gram_dir, name, args.kernel))
-        print("%s-%d\t%s\t%d seconds" % (args.kernel, args.n_iters, name, int(time.time() - t0)))
-    return 0
+    return gk.cli_run(args, lambda name, data, use_nl, use_el: [
+        (gram_file(args.gram_dir, name, args.kernel), sp_gram_matrix(data, use_nl) if args.kernel == "SP" else gr_gram_matrix(data, use_nl, use_el))])
 
 
 if __name__ == "__main__":

@@ -4285,6 +4285,25 @@ def hgt_message_pass(q, k, v, att, msg, pri, ix, scale):
     return hgt_pair_reduce(U, w_msg, ix)
 
 
+# ------------------------------------------------------------------------------------------------ graph-kernel switches
+class _GraphKernelSwitch:
+    """The base of wl_fused / gk_fused / kwl_fused / k3wl_fused: a context manager that sets its subclass's thread-local slot `_tls.fused`
+    to `on`, keeps the value it found and puts it back on exit (None: no override, the *_FUSED_DEFAULT holds)."""
+    _tls = None
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(self._tls, "fused", None)
+        self._tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        self._tls.fused = self.old
+        return False
+
+
 # ------------------------------------------------------------------------------------------------ WL / WLOA graph kernels
 # (dn_wl.hip; the dataset side -- reader, node classes, features, command line -- is graph_kernels.py)
 _wl_tls = _threading.local()
@@ -4300,22 +4319,11 @@ def wl_fused_enabled():
     return WL_FUSED_DEFAULT if m is None else m
 
 
-class wl_fused:
+class wl_fused(_GraphKernelSwitch):
     """Context manager: WL colour refinements started inside it (on this thread) sort in registers and LDS (on=True: dn_wl_refine_u64,
     lists of up to wl_max_entries() entries; longer ones take the composed path either way) or on the composed path (on=False: a
     device-wide segmented sort with torch ops, then dn_wl_fold_u64)."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_wl_tls, "fused", None)
-        _wl_tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _wl_tls.fused = self.old
-        return False
+    _tls = _wl_tls
 
 
 def wl_max_entries():
@@ -4396,21 +4404,10 @@ def gk_fused_enabled(kernel=None):
     return all(GK_FUSED_DEFAULT.values()) if kernel is None else GK_FUSED_DEFAULT[kernel]
 
 
-class gk_fused:
+class gk_fused(_GraphKernelSwitch):
     """Context manager: SP / GR feature builds started inside it (on this thread) run the dn_gk_* kernels (on=True; SP graphs above
     gk_sp_lds_max_nodes() nodes take the composed path either way) or the composed torch-op path (on=False)."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_gk_tls, "fused", None)
-        _gk_tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _gk_tls.fused = self.old
-        return False
+    _tls = _gk_tls
 
 
 def gk_sp_lds_max_nodes():
@@ -4453,22 +4450,11 @@ def kwl_fused_enabled():
     return KWL_FUSED_DEFAULT if m is None else m
 
 
-class kwl_fused:
+class kwl_fused(_GraphKernelSwitch):
     """Context manager: 2-WL refinements started inside it (on this thread) run the dn_kwl_* kernels (on=True; graphs above
     kwl_max_nodes() nodes (WL / DWL) or with a degree above kwl_max_entries() (LWL / LWLC) take the composed path either way) or the
     composed path (on=False: torch device ops, a device-wide segmented sort and dn_wl_fold_u64)."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_kwl_tls, "fused", None)
-        _kwl_tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _kwl_tls.fused = self.old
-        return False
+    _tls = _kwl_tls
 
 
 def kwl_max_nodes():
@@ -4551,22 +4537,11 @@ def k3wl_fused_enabled(kernel=None):
     return all(K3WL_FUSED_DEFAULT.values()) if kernel is None else K3WL_FUSED_DEFAULT[kernel]
 
 
-class k3wl_fused:
+class k3wl_fused(_GraphKernelSwitch):
     """Context manager: 3-WL refinements started inside it (on this thread) run the dn_k3wl_* kernels (on=True; graphs above
     k3wl_max_nodes() nodes (WL / DWL) or with a degree above k3wl_max_entries() (LWL / LWLC) take the composed path either way) or the
     composed path (on=False: torch device ops, a device-wide segmented sort and dn_wl_fold_u64)."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_k3wl_tls, "fused", None)
-        _k3wl_tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _k3wl_tls.fused = self.old
-        return False
+    _tls = _k3wl_tls
 
 
 def k3wl_max_nodes():
