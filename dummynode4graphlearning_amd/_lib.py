@@ -194,6 +194,13 @@ _SIGS = {
     "dn_k3wl_local_u64": (ctypes.c_int, [c_i64, c_i64, c_i64, P, c_i32, c_i32, c_i32] + [P] * 12 + [P]),
     "dn_k3wl_global_u64": (ctypes.c_int, [c_i64, c_i64, c_i64, P, P, c_i64, c_i32, c_i32] + [P] * 5 + [P]),
     "dn_k3wl_close_u64": (ctypes.c_int, [c_i64, c_i64, c_i32] + [P] * 9 + [P]),
+    "dn_seg_attn_max_keys": (c_i32, []),
+    "dn_seg_attn_wave_keys": (c_i32, []),
+    "dn_seg_attn_fwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i64] + [c_i32] * 5 + [P] * 7 + [c_f32, P, P, P]),
+    "dn_seg_attn_bwd_q_f32": (ctypes.c_int, [c_i64, c_i64, c_i64] + [c_i32] * 5 + [P] * 7 + [c_f32] + [P] * 4 + [P]),
+    "dn_seg_attn_bwd_kv_f32": (ctypes.c_int, [c_i64, c_i64, c_i64] + [c_i32] * 5 + [P] * 7 + [c_f32] + [P] * 5 + [P]),
+    "dn_seg_window_pool_fwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_i32] + [P] * 7 + [P]),
+    "dn_seg_window_pool_bwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_i32] + [P] * 6 + [P]),
 }
 
 _lib = None

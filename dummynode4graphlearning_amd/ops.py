@@ -4585,3 +4585,238 @@ def k3wl_close(num_nodes, malkin, tup_v, tup_w, tup_u, node_graph, node_ptr, csr
     require_gpu(tup_v, tup_w, tup_u, node_graph, node_ptr, csr_ptr, colors_in, work, colors_out)
     check(lib().dn_k3wl_close_u64(int(num_nodes), int(tup_v.numel()), int(bool(malkin)), ptr(tup_v), ptr(tup_w), ptr(tup_u), ptr(node_graph),
                                   ptr(node_ptr), ptr(csr_ptr), ptr(colors_in), ptr(work), ptr(colors_out), stream_ptr()), "dn_k3wl_close_u64")
+
+
+# ----------------------------------------------------------------------------------------------
+# SI count heads: ragged sparsemax / softmax attention and DIAMNet's window pooling (dn_seg_attn.hip)
+# ----------------------------------------------------------------------------------------------
+SEG_ATTN_MAX_H = 256
+SEG_ATTN_HEADS = (1, 2, 4, 8)
+SEG_ATTN_WAVE_KEYS = 64            # dn_seg_attn_wave_keys(): up to here a wavefront per (row, head)
+SEG_ATTN_MAX_KEYS = 1024           # dn_seg_attn_max_keys(): above, the composed path
+SEG_POOL_MAX_MEM = 64
+SEG_SCORES = {"sparsemax": 0, "softmax": 1}
+SEG_POOL_MODES = {"mean": 0, "sum": 1, "max": 2}
+_attn_tls = _threading.local()
+
+# The heads' default.  Measured on the scale batch (docs/LAB_NOTES.md "SI count heads: attention / DIAMNet"; 512 pairs, hidden 64, 4
+# heads, fused and composed alternated in one process): the MeanAttnPredictNet head 2.99 against 6.01 ms on the node rows and 15.6
+# against 35.2 ms on the edge rows, the DIAMNet heads 2.3 against 5.6 / 6.1 ms, the DMPNN step 15.9 against 25.2 ms (DIAMNet) and 29.0
+# against 53.9 ms (MeanAttnPredictNet), every fused round faster than every composed round -- outside the spread, so the fused
+# kernels are the default (as HGT_FUSED_DEFAULT).
+ATTN_FUSED_DEFAULT = True
+
+
+def attn_fused_enabled():
+    m = getattr(_attn_tls, "fused", None)
+    return ATTN_FUSED_DEFAULT if m is None else m
+
+
+class attn_fused:
+    """Context manager: seg_attention / seg_window_pool calls made inside it (on this thread) run on dn_seg_attn.hip (on=True) where
+    attn_fused_supported allows it, or on the composed path (on=False: the padded torch computation of attn_pred.py on the ragged rows)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_attn_tls, "fused", None)
+        _attn_tls.fused = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _attn_tls.fused = self.old
+        return False
+
+
+def attn_fused_supported(x, heads, max_k=1):
+    """The predicate of the fused attention: fp32 rows on the GPU, heads in {1, 2, 4, 8}, hidden <= 256, hidden / heads a power of two,
+    at most 1024 keys per pair."""
+    H, heads = int(x.shape[-1]), int(heads)
+    if not (x.is_cuda and x.dtype == torch.float32 and heads in SEG_ATTN_HEADS and 1 <= H <= SEG_ATTN_MAX_H and H % heads == 0):
+        return False
+    dk = H // heads
+    return dk & (dk - 1) == 0 and 1 <= int(max_k) <= SEG_ATTN_MAX_KEYS
+
+
+def _max_len(ptr_):
+    return int((ptr_[1:] - ptr_[:-1]).max()) if ptr_.numel() > 1 else 0
+
+
+def _pad_index(ptr_, L, n):
+    """(idx [B, L] long: the row of every left-aligned padded slot, clamped into the rows; valid [B, L] bool)."""
+    p = ptr_.long()
+    pos = torch.arange(int(L), device=ptr_.device).view(1, -1)
+    valid = pos < (p[1:] - p[:-1]).view(-1, 1)
+    idx = (p[:-1].view(-1, 1) + pos).clamp(max=max(int(n) - 1, 0))
+    return idx, valid
+
+
+class _SegAttnFn(torch.autograd.Function):
+    """out [Nq, H] of dn_seg_attn_fwd_f32; backward: dn_seg_attn_bwd_q_f32 (dq and the row terms) and dn_seg_attn_bwd_kv_f32 (dk, dv).
+    Saved: the inputs and stat [Nq, heads, 2].  Deterministic."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_ptr, k_ptr, heads, scale, score, q_skip, k_skip, max_q, max_k):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        require_gpu(q, k, v, q_ptr, k_ptr, q_skip, k_skip)
+        _i32(q_ptr, "q_ptr"), _i32(k_ptr, "k_ptr")
+        Nq, H = q.shape
+        Nk = k.shape[0]
+        B = q_ptr.numel() - 1
+        if k.shape != (Nk, H) or v.shape != (Nk, H) or k_ptr.numel() != B + 1 or B < 1:
+            raise _lib.DnHipError("seg_attention: q [Nq, H], k / v [Nk, H] and two pointer arrays over the same B >= 1 pairs expected")
+        if (q_skip is not None and q_skip.numel() != Nq) or (k_skip is not None and k_skip.numel() != Nk):
+            raise _lib.DnHipError("seg_attention: one skip flag per row expected")
+        out = torch.empty_like(q)
+        stat = torch.empty((Nq, heads, 2), dtype=torch.float32, device=q.device)
+        args = (B, Nq, Nk, H, heads, max_q, max_k, score, ptr(q_ptr), ptr(k_ptr), ptr(q_skip), ptr(k_skip), ptr(q), ptr(k), ptr(v), scale)
+        if Nq and Nk:
+            launch_tagged("seg_attn_fwd", lambda: check(lib().dn_seg_attn_fwd_f32(*args, ptr(out), ptr(stat), stream_ptr()),
+                                                       "dn_seg_attn_fwd_f32"))
+        else:
+            out.zero_()
+        ctx.args = (B, H, heads, max_q, max_k, score, scale, q_skip, k_skip)
+        ctx.save_for_backward(q, k, v, q_ptr, k_ptr, stat)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, q_ptr, k_ptr, stat = ctx.saved_tensors
+        B, H, heads, max_q, max_k, score, scale, q_skip, k_skip = ctx.args
+        dout = dout.contiguous()
+        Nq, Nk = q.shape[0], k.shape[0]
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        if not (Nq and Nk):
+            return (dq.zero_(), dk.zero_(), dv.zero_()) + (None,) * 9
+        rterm = torch.empty((Nq, heads), dtype=torch.float64, device=q.device)
+        args = (B, Nq, Nk, H, heads, max_q, max_k, score, ptr(q_ptr), ptr(k_ptr), ptr(q_skip), ptr(k_skip), ptr(q), ptr(k), ptr(v), scale,
+                ptr(stat))
+        launch_tagged("seg_attn_bwd_q", lambda: check(lib().dn_seg_attn_bwd_q_f32(*args, ptr(dout), ptr(dq), ptr(rterm), stream_ptr()),
+                                                     "dn_seg_attn_bwd_q_f32"))
+        launch_tagged("seg_attn_bwd_kv", lambda: check(lib().dn_seg_attn_bwd_kv_f32(*args, ptr(rterm), ptr(dout), ptr(dk), ptr(dv),
+                                                                                   stream_ptr()), "dn_seg_attn_bwd_kv_f32"))
+        return (dq, dk, dv) + (None,) * 9
+
+
+def seg_attention_composed(q, k, v, q_ptr, k_ptr, heads, scale, score="sparsemax", q_skip=None, k_skip=None, max_q=None, max_k=None):
+    """The same rows from the reference's algorithm: the rows padded to [B, L, H], the masked keys filled with -1e30, sparsemax or
+    softmax along the key axis, the masked query rows cleared (any dtype, any device)."""
+    from .subgraph_isomorphism.act import Sparsemax
+    Nq, H = q.shape
+    B, dk = q_ptr.numel() - 1, H // heads
+    Lq = int(max_q) if max_q is not None else _max_len(q_ptr)
+    Lk = int(max_k) if max_k is not None else _max_len(k_ptr)
+    if Nq == 0 or k.shape[0] == 0 or Lk == 0:
+        return q * 0
+    qi, qv = _pad_index(q_ptr, Lq, Nq)
+    ki, kv = _pad_index(k_ptr, Lk, k.shape[0])
+    if q_skip is not None:
+        qv = qv & ~q_skip.reshape(-1).bool()[qi]
+    if k_skip is not None:
+        kv = kv & ~k_skip.reshape(-1).bool()[ki]
+    qp, kp, vp = q[qi].view(B, Lq, heads, dk), k[ki].view(B, Lk, heads, dk), v[ki].view(B, Lk, heads, dk)
+    s = torch.einsum("bind,bjnd->bijn", qp, kp) * scale
+    s = s.masked_fill(~kv.view(B, 1, Lk, 1), -1e30)
+    s = Sparsemax(2)(s) if score == "sparsemax" else torch.softmax(s, dim=2)
+    s = s * kv.view(B, 1, Lk, 1).to(s.dtype)                           # (a pair without a live key: zero rows)
+    o = torch.einsum("bijn,bjnd->bind", s, vp).reshape(B, Lq, H).masked_fill(~qv.unsqueeze(-1), 0)
+    _, inside = _pad_index(q_ptr, Lq, Nq)
+    return o[inside]
+
+
+def seg_attention(q, k, v, q_ptr, k_ptr, heads, scale, score="sparsemax", q_skip=None, k_skip=None, max_q=None, max_k=None):
+    """out [Nq, hidden]: multi-head attention of the query rows of every pair over the pair's key rows with sparsemax or softmax
+    weights (module comment of dn_seg_attn.hip).  q [Nq, hidden], k / v [Nk, hidden] are the projected rows, ragged by q_ptr / k_ptr
+    [B + 1] int32; *_skip: uint8 / bool flags per row (a skipped key takes no weight, a skipped query row yields a zero row).
+    max_q / max_k: the largest row counts per pair when the caller knows them (the SI models do, from si_read_meta); otherwise they
+    are read back from the pointers.  The fused kernels where attn_fused_enabled() and attn_fused_supported (fp32, at most 1024
+    keys per pair), else the composed path."""
+    if score not in SEG_SCORES:
+        raise ValueError("seg_attention: score must be 'sparsemax' or 'softmax' (got %r)" % (score,))
+    heads = int(heads)
+    if q.dim() != 2 or q.shape[1] % heads != 0:
+        raise _lib.DnHipError("seg_attention: q [Nq, hidden] with hidden %% heads == 0 expected")
+    if max_q is None:
+        max_q = _max_len(q_ptr)
+    if max_k is None:
+        max_k = _max_len(k_ptr)
+    if (attn_fused_enabled() and q.dtype == k.dtype == v.dtype and k.is_cuda and v.is_cuda
+            and attn_fused_supported(q, heads, max(int(max_k), 1)) and q.shape[0] and k.shape[0] and max_q >= 1 and max_k >= 1):
+        return _SegAttnFn.apply(q, k, v, q_ptr, k_ptr, heads, float(scale), SEG_SCORES[score], _u8_or_none(q_skip), _u8_or_none(k_skip),
+                                int(max_q), int(max_k))
+    return seg_attention_composed(q, k, v, q_ptr, k_ptr, heads, float(scale), score, q_skip, k_skip, max_q, max_k)
+
+
+class _SegWindowPoolFn(torch.autograd.Function):
+    """(mem [B mem_len, D], mem_mask [B, mem_len]) of dn_seg_window_pool_fwd_f32; the backward gathers per row (dn_seg_window_pool_bwd_f32)."""
+
+    @staticmethod
+    def forward(ctx, rows, ptr_, skip, mem_len, mode):
+        rows = rows.contiguous()
+        require_gpu(rows, ptr_, skip)
+        _i32(ptr_, "ptr")
+        N, D = rows.shape
+        B = ptr_.numel() - 1
+        dev = rows.device
+        mem = torch.empty((B * mem_len, D), dtype=torch.float32, device=dev)
+        mask = torch.empty((B, mem_len), dtype=torch.bool, device=dev)
+        arg = torch.empty((B * mem_len, D), dtype=I32, device=dev) if mode == SEG_POOL_MODES["max"] else None
+        span = torch.empty((B, 2), dtype=I32, device=dev)
+        launch_tagged("seg_window_pool", lambda: check(lib().dn_seg_window_pool_fwd_f32(
+            B, N, D, mem_len, mode, ptr(ptr_), ptr(skip), ptr(rows), ptr(mem), ptr(mask.view(torch.uint8)), ptr(arg), ptr(span),
+            stream_ptr()), "dn_seg_window_pool_fwd_f32"))
+        ctx.args = (B, N, D, mem_len, mode, skip, arg)
+        ctx.save_for_backward(ptr_, span)
+        ctx.mark_non_differentiable(mask)
+        return mem, mask
+
+    @staticmethod
+    def backward(ctx, dmem, _dmask):
+        ptr_, span = ctx.saved_tensors
+        B, N, D, mem_len, mode, skip, arg = ctx.args
+        dmem = dmem.contiguous()
+        drows = torch.empty((N, D), dtype=torch.float32, device=dmem.device)
+        launch_tagged("seg_window_pool_bwd", lambda: check(lib().dn_seg_window_pool_bwd_f32(
+            B, N, D, mem_len, mode, ptr(ptr_), ptr(skip), ptr(span), ptr(arg), ptr(dmem), ptr(drows), stream_ptr()),
+            "dn_seg_window_pool_bwd_f32"))
+        return drows, None, None, None, None
+
+
+def seg_window_pool_composed(rows, ptr_, skip, mem_len, mode, max_len=None):
+    """The same memory from attn_pred.init_mem on the padded rows, one group per distinct span (any dtype, any device)."""
+    from .subgraph_isomorphism.attn_pred import init_mem
+    from .subgraph_isomorphism.dl import batch_convert_mask_to_start_and_end
+    N, D = rows.shape
+    B = ptr_.numel() - 1
+    L = int(max_len) if max_len is not None else _max_len(ptr_)
+    idx, valid = _pad_index(ptr_, max(L, 1), N)
+    if skip is not None:
+        valid = valid & ~skip.reshape(-1).bool()[idx]
+    x = rows[idx].masked_fill(~valid.unsqueeze(-1), 0)
+    start, end = batch_convert_mask_to_start_and_end(valid)
+    uniq, inv = torch.unique(torch.stack([start, end + 1], dim=1), dim=0, return_inverse=True)
+    mem = rows.new_zeros((B, mem_len, D))
+    mask = torch.zeros((B, mem_len), dtype=torch.bool, device=rows.device)
+    for i, (s, e) in enumerate(uniq.tolist()):
+        sel = torch.nonzero(inv == i).view(-1)
+        m, mk = init_mem(x[sel, s:e], valid[sel, s:e], mem_len, mode)
+        mem = mem.index_copy(0, sel, m)
+        mask = mask.index_copy(0, sel, mk.bool())
+    return mem.reshape(B * mem_len, D), mask
+
+
+def seg_window_pool(rows, ptr_, skip, mem_len, mode, max_len=None):
+    """DIAMNet's initial memory of every segment of rows [N, D] (ptr_ [B + 1] int32): (mem [B mem_len, D], mem_mask [B, mem_len] bool).
+    Per segment the rows from the first to the last with skip == 0 (L rows; skipped rows inside count as zero rows): L <= mem_len gives
+    those rows behind mem_len - L zero rows, else the mean | sum | max of the mem_len windows of L - (mem_len - 1) stride rows every
+    stride = L // mem_len rows.  mem_mask: the window holds an unskipped row."""
+    if mode not in SEG_POOL_MODES:
+        raise NotImplementedError("seg_window_pool: mode=%s (mean, sum and max are built)" % (mode,))
+    mem_len = int(mem_len)
+    if rows.dim() != 2 or mem_len < 1:
+        raise _lib.DnHipError("seg_window_pool: rows [N, D] and mem_len >= 1 expected")
+    if (attn_fused_enabled() and rows.is_cuda and rows.dtype == torch.float32 and rows.shape[0] and rows.shape[1]
+            and mem_len <= SEG_POOL_MAX_MEM and ptr_.numel() > 1):
+        return _SegWindowPoolFn.apply(rows, ptr_, _u8_or_none(skip), mem_len, SEG_POOL_MODES[mode])
+    return seg_window_pool_composed(rows, ptr_, skip, mem_len, mode, max_len)

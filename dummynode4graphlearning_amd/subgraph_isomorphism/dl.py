@@ -45,3 +45,16 @@ def split_and_batchify_graph_feats(batched_graph_feats, graph_sizes, pre_pad=Fal
         return feats.to(batched_graph_feats.dtype), mask
     feats = _PadRows.apply(x2, slot_ptr, slot_src, row_slot, (bsz, max_size, x2.shape[1]))
     return feats, mask
+
+
+def batch_convert_mask_to_start_and_end(mask):
+    """dl.py:130-135: per row of a [B, L] mask the first unmasked index and the LAST unmasked index (the reference's `end`: the first
+    index at which the cumulative sum reaches its maximum; `0 0 1 1 0 1 0 0` gives 2 and 5).  A row without any unmasked position
+    gives (0, 0), as there.  Computed from the positions themselves, so the result does not depend on how a device breaks ties."""
+    m = mask != 0
+    L = m.size(-1)
+    pos = th.arange(L, device=mask.device).expand_as(m)
+    start = pos.masked_fill(~m, L).min(dim=-1)[0]
+    start = th.where(m.any(dim=-1), start, th.zeros_like(start))
+    end = pos.masked_fill(~m, 0).max(dim=-1)[0]
+    return start, end

@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from .attn_pred import ATTN_PRED_NETS, BaseAttnPredictNet, DIAMNet, MaxAttnPredictNet, MeanAttnPredictNet, build_attn_pred_net
 from .dl import split_and_batchify_graph_feats
 from .pred import MaxPredictNet, MeanPredictNet, SumPredictNet
 from .rgcn import RGCNRepNet
@@ -30,6 +31,98 @@ from .rgin import RGINRepNet
 NODEID, NODELABEL, EDGELABEL, DUMMYFLAG = "id", "label", "label", "is_dummy"      # constants.py:14-23
 _UNSUPPORTED_PRED_NETS = ("MeanAttnPredictNet", "SumAttnPredictNet", "MaxAttnPredictNet", "MeanMemAttnPredictNet",
                           "SumMemAttnPredictNet", "MaxMemAttnPredictNet", "DIAMNet")
+_ATTN_HEADS = (BaseAttnPredictNet, DIAMNet)
+
+
+def _constructor_refusal(pred_net):
+    if pred_net in ATTN_PRED_NETS:
+        return ("pred_net=%s is not accepted by the constructor; build the model with one of the pooling heads and attach it with "
+                "model.set_pred_net(%r, **kw)" % (pred_net, pred_net))
+    return "pred_net=%s is not provided by this package (the memory-attention heads are out of scope, DESIGN.md 7)" % pred_net
+
+
+def _is_attn_head(net):
+    nets = net.values() if isinstance(net, nn.ModuleDict) else (net,)
+    return any(isinstance(n, _ATTN_HEADS) for n in nets)
+
+
+def attn_ragged_ok(net, training):
+    """Can the steps of this attention head run on ops.seg_attention?  The attentions as the heads build them: projected (hidden_dim
+    != -1), no zero key, no input layer norms, no active dropout inside.  Anything else goes through the padded modules."""
+    return all(a.weight_q is not None and a.weight_v is not None and not a.add_zero_attn and not a.pre_lnorm
+               and a.score_func in ops.SEG_SCORES and not (training and a.drop.p > 0) for a in (net.p_attn, net.g_attn))
+
+
+def attn_steps_ragged(net, p_rows, p_ptr, p_skip, Lp, g_rows, g_ptr, g_skip, Lg):
+    """The inference steps of BaseAttnPredictNet on the ragged rows [Np, D] / [Ng, D] (skipped rows already zero): per step the graph
+    rows attend to the pattern rows and then to themselves.  Returns the refined graph rows; skipped rows stay zero rows."""
+    pa, ga = net.p_attn, net.g_attn
+    pk, pv = _proj(p_rows, pa.weight_k), _proj(p_rows, pa.weight_v)
+    g = g_rows
+    for _ in range(net.infer_steps):
+        a = ops.seg_attention(_proj(g, pa.weight_q), pk, pv, g_ptr, p_ptr, pa.num_heads, pa.scale, pa.score_func, g_skip, p_skip,
+                              max_q=Lg, max_k=Lp)
+        g = pa.close(g, _proj(a, pa.weight_o))
+        a = ops.seg_attention(_proj(g, ga.weight_q), _proj(g, ga.weight_k), _proj(g, ga.weight_v), g_ptr, g_ptr, ga.num_heads,
+                              ga.scale, ga.score_func, g_skip, g_skip, max_q=Lg, max_k=Lg)
+        g = ga.close(g, _proj(a, ga.weight_o))
+    return g
+
+
+def diamnet_memory_ragged(net, p_rows, p_ptr, p_skip, Lp, g_rows, g_ptr, g_skip, Lg):
+    """DIAMNet's memory on the ragged rows: the window pool of the graph rows, mem_layer, then infer_steps rounds with the mem_len
+    memory rows of every pair as the queries.  Returns the flattened memory [B, mem_len * hidden]."""
+    B, M = g_ptr.numel() - 1, net.mem_len
+    mem, m_mask = ops.seg_window_pool(g_rows, g_ptr, g_skip, M, net.mem_init, max_len=Lg)
+    m = ops.linear_any(mem, net.mem_layer.weight, net.mem_layer.bias)
+    m_ptr = th.arange(0, (B + 1) * M, M, dtype=th.int32, device=m.device)
+    m_skip = (~m_mask).reshape(-1).view(th.uint8)
+    pa, ga = net.p_attn, net.g_attn
+    pk, pv = _proj(p_rows, pa.weight_k), _proj(p_rows, pa.weight_v)
+    gk, gv = _proj(g_rows, ga.weight_k), _proj(g_rows, ga.weight_v)
+    for _ in range(net.infer_steps):
+        a = ops.seg_attention(_proj(m, pa.weight_q), pk, pv, m_ptr, p_ptr, pa.num_heads, pa.scale, pa.score_func, m_skip, p_skip,
+                              max_q=M, max_k=Lp)
+        m = pa.close(m, _proj(a, pa.weight_o))
+        a = ops.seg_attention(_proj(m, ga.weight_q), gk, gv, m_ptr, g_ptr, ga.num_heads, ga.scale, ga.score_func, m_skip, g_skip,
+                              max_q=M, max_k=Lg)
+        m = ga.close(m, _proj(a, ga.weight_o))
+    return m.reshape(B, -1)
+
+
+def _proj(x, w):
+    """x @ w for a parameter stored [in, out] (the attention weights), on the any-width HIP product."""
+    return ops.linear_any(x.contiguous(), w.t().contiguous())
+
+
+def _zero_skipped(rows, skip):
+    return rows if skip is None else rows.masked_fill(skip.reshape(-1, 1).bool(), 0)
+
+
+def attn_head_ragged(net, p_rows, p_ptr, p_skip, Lp, p_count, g_rows, g_ptr, g_skip, Lg, g_count):
+    """forward of an attention head or of DIAMNet (return_weights off, no dropout) on ragged rows: the steps on ops.seg_attention /
+    ops.seg_window_pool, the closing pool on dn_si_pool_sum / dn_si_pool_max with the bias as the value of every padded position."""
+    p_skip, g_skip = ops._u8_or_none(p_skip), ops._u8_or_none(g_skip)
+    p_rows, g_rows = _zero_skipped(p_rows, p_skip).contiguous(), _zero_skipped(g_rows, g_skip).contiguous()
+    dt = g_rows.dtype
+    pl, gl = p_count.to(th.float32).view(-1, 1), g_count.to(th.float32).view(-1, 1)
+    pl_inv, gl_inv = (1.0 / pl).to(dt), (1.0 / gl).to(dt)
+    pl, gl = pl.to(dt), gl.to(dt)
+    if isinstance(net, DIAMNet):
+        m = diamnet_memory_ragged(net, p_rows, p_ptr, p_skip, Lp, g_rows, g_ptr, g_skip, Lg)
+        return net.close_memory(m, pl, gl, pl_inv, gl_inv)
+    g_rows = attn_steps_ragged(net, p_rows, p_ptr, p_skip, Lp, g_rows, g_ptr, g_skip, Lg)
+    pooled = []
+    for rows, fc, ptr, skip, L in ((p_rows, net.p_fc, p_ptr, p_skip, Lp), (g_rows, net.g_fc, g_ptr, g_skip, Lg)):
+        if isinstance(net, MaxAttnPredictNet):
+            pooled.append(ops.si_pool_max(ops.linear_any(rows.contiguous(), fc.weight, fc.bias), fc.bias, ptr, L, skip))
+            continue
+        S, _ = ops.si_pool_sum(rows.contiguous(), ptr, skip)
+        y = th.addmm(fc.bias.float() * L, S, fc.weight.float().t())
+        pooled.append((y / L if isinstance(net, MeanAttnPredictNet) else y).to(dt))
+    p, g = pooled
+    y = net.act(net.pred_fc1(th.cat([p, g, g - p, g * p, pl, gl, pl_inv, gl_inv], dim=1)))
+    return net.pred_fc2(th.cat([y, pl, gl, pl_inv, gl_inv], dim=1))
 
 
 # ------------------------------------------------------------------------------------------------ container.py:14-100
@@ -314,9 +407,20 @@ class GraphAdjModel(nn.Module):
             return classes[pred_net](self.get_rep_dim(), hidden_dim=hidden_dim, act_func=act_func, dropout=dropout,
                                      return_weights="node" in return_weights)
         if pred_net in _UNSUPPORTED_PRED_NETS:
-            raise NotImplementedError("pred_net=%s is not provided by this package (attention / memory / DIAMNet heads are out "
-                                      "of scope)" % pred_net)
+            raise NotImplementedError(_constructor_refusal(pred_net))
         raise ValueError(pred_net)
+
+    def set_pred_net(self, pred_net, **kw):
+        """Replace self.pred_net by one of the attention heads or DIAMNet (attn_pred.py), built at get_rep_dim() from the keys of
+        the reference's create_pred_net (pred_hid_dim, pred_act_func, pred_dropout, pred_return_weights, pred_num_heads,
+        pred_infer_steps, pred_mem_len, pred_mem_init; same defaults).  The new head starts from its own fresh initial values, on
+        the device and in the dtype of the head it replaces.  Returns the new head."""
+        new = build_attn_pred_net(pred_net, self.get_rep_dim(), "node" in kw.get("pred_return_weights", "none"), **kw)
+        old = next(self.pred_net.parameters())
+        new = new.to(device=old.device, dtype=old.dtype)
+        del self.pred_net
+        self.pred_net = new
+        return new
 
     def get_graph_enc_dims(self):
         return OrderedDict({"v": get_enc_len(self.max_ngv - 1, self.base) * self.base,
@@ -407,8 +511,9 @@ class GraphAdjModel(nn.Module):
 
     def _ragged_head_applies(self):
         net = self.pred_net
-        return (type(net) in (SumPredictNet, MeanPredictNet, MaxPredictNet) and net.weight_fc1 is None
-                and not (self.training and net.drop.p > 0)
+        return ((type(net) in (SumPredictNet, MeanPredictNet, MaxPredictNet)
+                 or (isinstance(net, _ATTN_HEADS) and attn_ragged_ok(net, self.training)))
+                and net.weight_fc1 is None and not (self.training and net.drop.p > 0)
                 and type(self).refine_node_weights is GraphAdjModel.refine_node_weights)
 
     def _degrees(self, g):
@@ -431,6 +536,11 @@ class GraphAdjModel(nn.Module):
         (sum of the unmasked rows) @ W^T + L * b (/ L for Mean).  Max: fc per row, then the per-graph max with b as the
         candidate of the masked positions."""
         net = self.pred_net
+        if isinstance(net, _ATTN_HEADS):
+            rows = [th.cat(self._addfeat(s) + [s[1]], dim=1) if (self.pred_with_enc or self.pred_with_deg) else s[1]
+                    for s in (p_side, g_side)]
+            return attn_head_ragged(net, rows[0], p_side[2], p_side[6], p_side[7], p_v_mask.sum(1),
+                                    rows[1], g_side[2], g_side[6], g_side[7], g_v_mask.sum(1))
         pooled, counts = [], []
         for side, fc in ((p_side, net.p_fc), (g_side, net.g_fc)):
             g, rep, ptr, ids, labels, enc_net, dummy, L = side
@@ -478,6 +588,9 @@ class GraphAdjModel(nn.Module):
         the end of the state_dict.  On failure the sizes AND the modules (and their order) are restored."""
         if "base" in kw and kw["base"] != self.base:
             raise ValueError("expand cannot change base (%s -> %s)" % (self.base, kw["base"]))
+        if _is_attn_head(self.pred_net):
+            raise NotImplementedError("expand: a model that carries an attention head or DIAMNet (set_pred_net) cannot be expanded; "
+                                      "expand first, then attach the head")
         kw = dict(kw)
         names = ["max_npv", "max_npvl", "max_npe", "max_npel", "max_ngv", "max_ngvl", "max_nge", "max_ngel"]
         bak = {k: getattr(self, k) for k in names}

@@ -24,7 +24,8 @@ from .. import ops
 from .._lib import DnHipError
 from .dl import split_and_batchify_graph_feats
 from .dual import CompGCNLayer, DMPLayer
-from .graph_adj import (_UNSUPPORTED_PRED_NETS, DUMMYFLAG, EDGELABEL, NODEID, NODELABEL, EquivariantEmbedding, GraphAdjModel,
+from .attn_pred import build_attn_pred_net
+from .graph_adj import (_ATTN_HEADS, _UNSUPPORTED_PRED_NETS, _constructor_refusal, attn_head_ragged, attn_ragged_ok, DUMMYFLAG, EDGELABEL, NODEID, NODELABEL, EquivariantEmbedding, GraphAdjModel,
                         MultihotEmbedding, NormalEmbedding, OrthogonalEmbedding, OutputDict, PositionEmbedding, ScalarFilter,
                         UniformEmbedding, _i32, get_enc_len)
 from .pred import MaxPredictNet, MeanPredictNet, SumPredictNet
@@ -103,9 +104,21 @@ class GraphAdjModelV2(GraphAdjModel):
                 "e": cls(rep_e_dim, hidden_dim=hidden_dim, act_func=act_func, dropout=dropout,
                          return_weights="edge" in return_weights) if self.edge_pred else None})
         if pred_net in _UNSUPPORTED_PRED_NETS:
-            raise NotImplementedError("pred_net=%s is not provided by this package (attention / memory / DIAMNet heads are out "
-                                      "of scope)" % pred_net)
+            raise NotImplementedError(_constructor_refusal(pred_net))
         raise ValueError(pred_net)
+
+    def set_pred_net(self, pred_net, **kw):
+        """GraphAdjModel.set_pred_net for the {"v", "e"} pair of heads (a switched-off side stays a None entry)."""
+        return_weights = kw.get("pred_return_weights", "none")
+        rep_v_dim, rep_e_dim = self.get_rep_dim()
+        new = nn.ModuleDict({
+            "v": build_attn_pred_net(pred_net, rep_v_dim, "node" in return_weights, **kw) if self.node_pred else None,
+            "e": build_attn_pred_net(pred_net, rep_e_dim, "edge" in return_weights, **kw) if self.edge_pred else None})
+        old = next(self.pred_net.parameters())
+        new = new.to(device=old.device, dtype=old.dtype)
+        del self.pred_net
+        self.pred_net = new
+        return new
 
     def get_graph_enc_dims(self):
         return OrderedDict({"v": get_enc_len(self.max_ngv - 1, self.base) * self.base,
@@ -275,8 +288,9 @@ class GraphAdjModelV2(GraphAdjModel):
 
     # ---- heads ----
     def _ragged_applies(self, net):
-        return (type(net) in (SumPredictNet, MeanPredictNet, MaxPredictNet) and net.weight_fc1 is None
-                and not (self.training and net.drop.p > 0)
+        return ((type(net) in (SumPredictNet, MeanPredictNet, MaxPredictNet)
+                 or (isinstance(net, _ATTN_HEADS) and attn_ragged_ok(net, self.training)))
+                and net.weight_fc1 is None and not (self.training and net.drop.p > 0)
                 and type(self).refine_node_weights is GraphAdjModel.refine_node_weights
                 and type(self).refine_edge_weights is GraphAdjModel.refine_edge_weights)
 
@@ -319,6 +333,12 @@ class GraphAdjModelV2(GraphAdjModel):
     def _ragged(self, kind, net, P, G):
         """PredictNet.forward on the ragged rows (see GraphAdjModel._ragged_head): Sum / Mean pool the rows first (fc is linear),
         Max applies fc per row and takes the per-graph max with the bias as the candidate of the masked positions."""
+        if isinstance(net, _ATTN_HEADS):
+            a = []
+            for s in (P, G):
+                ptr, skip, L = (s["ptr"], s["dummy"], s["L"]) if kind == "v" else (s["eptr"], s["skip"], s["Le"])
+                a += [self._rows(kind, s), ptr, skip, L, s[kind + "_mask"].sum(1)]
+            return attn_head_ragged(net, *a)
         pooled, counts = [], []
         for s, fc in ((P, net.p_fc), (G, net.g_fc)):
             ptr, skip, L = (s["ptr"], s["dummy"], s["L"]) if kind == "v" else (s["eptr"], s["skip"], s["Le"])

@@ -4,6 +4,7 @@ Same RNG consumption as the reference (one nn.init.uniform_ per tensor), so the 
 gives bit-identical initial weights (tests/test_host_logic.py pins this against the golden fixtures)."""
 import math
 
+import torch as th
 import torch.nn as nn
 
 from .act import LEAKY_RELU_A
@@ -48,10 +49,35 @@ def kaiming_normal_init(x, gain=1.0):
     return nn.init.normal_(x, 0, gain / math.sqrt(fan_in))
 
 
+def identity_init(x, gain=1.0):
+    """init.py:105-122: eye_ (ones_ for a vector) plus N(0, 1) * std**2 with std = gain * 2 / (fan_in + fan_out) (sic: no root, and the
+    square); tensors of more dimensions are viewed with their last two folded."""
+    with th.no_grad():
+        size = tuple(x.size())
+        if len(size) <= 2:
+            fan_in, fan_out = calculate_fan_in_and_fan_out(x)
+            std = gain * (2.0 / float(fan_in + fan_out))
+            if len(size) == 1:
+                nn.init.ones_(x)
+            else:
+                nn.init.eye_(x)
+            x += th.randn_like(x) * std ** 2
+        else:
+            identity_init(x.view(size[:-2] + (-1,)), gain=gain)
+    return x
+
+
 def init_weight(x, activation="none", init="uniform"):
-    """init.py:125-143 ('uniform', 'normal' and 'zero' are the branches the built layers reach)."""
+    """init.py:125-143 ('uniform', 'normal', 'zero' and 'identity' are the branches the built layers reach).  Anything that is not a
+    tensor -- an nn.Module, say -- is left as it is, as in the reference (its isinstance(x, th.Tensor) guard)."""
     gain = calculate_gain(activation)
-    if init == "uniform":
+    if init not in ("uniform", "normal", "zero", "identity"):
+        raise ValueError("init=%s is not supported now." % init)
+    if not isinstance(x, th.Tensor):
+        return
+    if init == "identity":
+        identity_init(x, gain=gain)
+    elif init == "uniform":
         xavier_uniform_init(x, gain=gain)
     elif init == "normal":
         kaiming_normal_init(x, gain=gain)

@@ -1183,6 +1183,44 @@ int dn_k3wl_close_u64(int64_t num_nodes, int64_t num_items, int32_t malkin, cons
                       const int32_t* node_graph, const int32_t* node_ptr, const int32_t* ptr, const int64_t* colors_in, const int64_t* work,
                       int64_t* colors_out, dn_stream_t stream);
 
+/* ---- ragged sparsemax / softmax attention and DIAMNet's window pooling (dn_seg_attn.hip) ----------------------------------------
+ * B pairs; pair b owns the query rows q_ptr[b] .. q_ptr[b + 1] of q [Nq, H] and the key rows k_ptr[b] .. k_ptr[b + 1] of k, v [Nk, H]
+ * (fp32, already projected); head h owns the columns h dk .. (h + 1) dk, dk = H / heads.  heads in {1, 2, 4, 8}, H <= 256, dk a power
+ * of two.  q_skip [Nq] / k_skip [Nk] (NULL: none): a key with a flag takes no weight, a query row with a flag (or of a pair without
+ * a live key) yields a zero row.  max_q / max_k: the largest row counts of a pair (the caller's: the kernels clamp to them);
+ * max_k <= dn_seg_attn_max_keys(), and the forward runs its one-wavefront-per-row form where max_k <= dn_seg_attn_wave_keys().
+ *   fwd:    out [Nq, H] = sum_j p_j v_j per head, p = sparsemax or softmax of scale <q_i, k_j> over the live keys;
+ *           stat [Nq, heads, 2] = {max, tau} (sparsemax: p_j = max(z_j - max - tau, 0)) or {max, sum exp(z - max)}.
+ *   bwd_q:  dq [Nq, H] and rterm [Nq, heads] in fp64 (the mean of dP over the support, or sum p dP) from stat and dout [Nq, H].
+ *   bwd_kv: dk, dv [Nk, H] from stat, rterm and dout; the query rows of a pair are walked in order.  No atomics anywhere. */
+#define DN_SCORE_SPARSEMAX 0
+#define DN_SCORE_SOFTMAX 1
+int32_t dn_seg_attn_max_keys(void);
+int32_t dn_seg_attn_wave_keys(void);
+int dn_seg_attn_fwd_f32(int64_t B, int64_t Nq, int64_t Nk, int32_t H, int32_t heads, int32_t max_q, int32_t max_k, int32_t score,
+                        const int32_t* q_ptr, const int32_t* k_ptr, const uint8_t* q_skip, const uint8_t* k_skip, const float* q,
+                        const float* k, const float* v, float scale, float* out, float* stat, dn_stream_t stream);
+int dn_seg_attn_bwd_q_f32(int64_t B, int64_t Nq, int64_t Nk, int32_t H, int32_t heads, int32_t max_q, int32_t max_k, int32_t score,
+                          const int32_t* q_ptr, const int32_t* k_ptr, const uint8_t* q_skip, const uint8_t* k_skip, const float* q,
+                          const float* k, const float* v, float scale, const float* stat, const float* dout, float* dq, double* rterm,
+                          dn_stream_t stream);
+int dn_seg_attn_bwd_kv_f32(int64_t B, int64_t Nq, int64_t Nk, int32_t H, int32_t heads, int32_t max_q, int32_t max_k, int32_t score,
+                           const int32_t* q_ptr, const int32_t* k_ptr, const uint8_t* q_skip, const uint8_t* k_skip, const float* q,
+                           const float* k, const float* v, float scale, const float* stat, const double* rterm, const float* dout,
+                           float* dk, float* dv, dn_stream_t stream);
+/* dn_seg_window_pool_*: per segment b of rows [N, D] (ptr [B + 1]) the span = the rows first .. last with skip == 0 (L of them; a
+ * skipped row inside is a zero row) gives mem_len rows of mem [B mem_len, D]: L <= mem_len: the span's rows behind mem_len - L zero
+ * rows; else window m = the kernel = L - (mem_len - 1) stride rows from m stride on, stride = L / mem_len, as their mean, sum or max.
+ * mem_mask [B, mem_len] = the window holds a row with skip == 0; span [B, 2] = {first, L}; arg [B mem_len, D] (max only) = the row
+ * that won, -1 where a zero row did.  bwd: drows [N, D], every row gathering from the windows that hold it. */
+#define DN_POOL_MEAN 0
+#define DN_POOL_SUM 1
+#define DN_POOL_MAX 2
+int dn_seg_window_pool_fwd_f32(int64_t B, int64_t N, int32_t D, int32_t mem_len, int32_t mode, const int32_t* ptr, const uint8_t* skip,
+                               const float* rows, float* mem, uint8_t* mem_mask, int32_t* arg, int32_t* span, dn_stream_t stream);
+int dn_seg_window_pool_bwd_f32(int64_t B, int64_t N, int32_t D, int32_t mem_len, int32_t mode, const int32_t* ptr, const uint8_t* skip,
+                               const int32_t* span, const int32_t* arg, const float* dmem, float* drows, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,284 @@
+"""GPU tests of ops.seg_attention and ops.seg_window_pool (dn_seg_attn.hip) against the float64 restatement of tests/seg_attn_ref.py.
+
+Bound: 1e-4 of the reference tensor's largest magnitude, for the output and for the gradients of q, k and v.  Sparsemax's gradient
+jumps where a score crosses the threshold, so every case's seed was chosen (on the CPU: `python tests/test_gpu_seg_attn.py` prints
+the table) so that the float64 reference keeps |z - tau| >= 1e-3 for every live key of every live query row; each test asserts that
+margin on the reference alone before it compares, so a case that loses it fails loudly instead of flaking.
+
+Where a gradient is zero in exact arithmetic (a support of one key: dz = dP - mean(dP) = 0, so dq = dk = 0; every pm80 sparsemax row
+is such a row) the reference tensor holds float64 roundoff only and has no magnitude to be relative to.  There the kernel's result
+is held to 1e-4 of the magnitude of the TERMS that cancel (dq: scale max|dP| max|k|, dk: scale max|dP| max|q|), and the test first
+asserts that the reference is below 1e-9 of that magnitude, so the rule cannot apply to a tensor that has a magnitude of its own."""
+import numpy as np
+import pytest
+import torch
+
+import seg_attn_ref as R
+
+DEV = "cuda:0"
+RTOL = 1e-4
+MARGIN = 1e-3
+SCORES = ("sparsemax", "softmax")
+
+# name: (query rows per pair, key rows per pair, hidden, heads, score spread, skipped query rows, skipped key rows)
+CASES = {
+    "k1": ([4], [1], 16, 4, 3.0, [], []),
+    "k2_b1": ([1], [2], 64, 1, 3.0, [], []),
+    "k63": ([4], [63], 64, 4, 3.0, [], []),
+    "k64_h256": ([4], [64], 256, 8, 3.0, [], []),
+    "k65": ([4], [65], 64, 4, 3.0, [], []),
+    "k300": ([4], [300], 64, 4, 3.0, [], []),
+    "k1024": ([4], [1024], 16, 4, 3.0, [], []),
+    "k1025_composed": ([4], [1025], 16, 4, 3.0, [], []),
+    "q65": ([65, 1], [7, 3], 64, 4, 4.0, [], []),
+    "q65_block": ([65], [70], 16, 4, 4.0, [], []),
+    "mixed": ([4, 1, 9, 2], [5, 64, 1, 17], 64, 4, 3.0, [], []),
+    "mixed_block": ([3, 5, 1], [65, 2, 130], 64, 1, 3.0, [], []),
+    "skips": ([5, 3], [6, 4], 64, 4, 3.0, [2, 5], [3, 6]),
+    "skips_block": ([5, 3], [80, 4], 16, 4, 3.0, [0, 7], [40, 81]),
+    "one_live_key": ([3, 2], [4, 3], 16, 4, 3.0, [], [0, 1, 3, 4, 6]),
+    "pm80": ([4], [20], 64, 4, 80.0, [], []),
+    "pm80_block": ([4], [100], 64, 4, 80.0, [], []),
+    "spread1": ([5, 3], [6, 4], 64, 4, 1.0, [2, 5], [3, 6]),
+}
+SEEDS = {"k1": 0, "k2_b1": 0, "k63": 0, "k64_h256": 0, "k65": 0, "k300": 0, "k1024": 0, "k1025_composed": 0, "q65": 3, "q65_block": 0,
+         "mixed": 0, "mixed_block": 0, "skips": 0, "skips_block": 0, "one_live_key": 0, "pm80": 0, "pm80_block": 0, "spread1": 0}
+
+
+def _ptr(lens):
+    return torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32)
+
+
+def make_case(name, seed):
+    ql, kl, H, heads, spread, qs, ks = CASES[name]
+    g = torch.Generator().manual_seed(seed)
+    dk = H // heads
+    Nq, Nk = sum(ql), sum(kl)
+    q = torch.randn(Nq, H, generator=g)
+    k = torch.randn(Nk, H, generator=g)
+    v = torch.randn(Nk, H, generator=g)
+    scale = spread / dk ** 0.5                               # z = scale <q, k> ~ N(0, spread^2)
+    q_skip = torch.zeros(Nq, dtype=torch.bool)
+    k_skip = torch.zeros(Nk, dtype=torch.bool)
+    q_skip[qs] = True
+    k_skip[ks] = True
+    coef = torch.randn(Nq, H, generator=g)
+    return dict(q=q, k=k, v=v, q_ptr=_ptr(ql), k_ptr=_ptr(kl), heads=heads, scale=scale, q_skip=q_skip if qs else None,
+                k_skip=k_skip if ks else None, coef=coef, max_q=max(ql), max_k=max(kl))
+
+
+def reference(c, score):
+    q, k, v = (c[n].double().requires_grad_(True) for n in "qkv")
+    out, margin = R.seg_attention(q, k, v, c["q_ptr"], c["k_ptr"], c["heads"], c["scale"], score, c["q_skip"], c["k_skip"])
+    (out * c["coef"].double()).sum().backward()
+    heads = c["heads"]
+    dP = torch.einsum("ind,jnd->inj", c["coef"].double().view(q.shape[0], heads, -1), c["v"].double().view(k.shape[0], heads, -1))
+    terms = dict(dq=float(c["scale"] * dP.abs().max() * c["k"].abs().max()), dk=float(c["scale"] * dP.abs().max() * c["q"].abs().max()))
+    return dict(out=out.detach(), dq=q.grad, dk=k.grad, dv=v.grad, margin=margin, terms=terms)
+
+
+def run_gpu(c, score, give_max=True):
+    from dummynode4graphlearning_amd import ops
+    t = lambda x: None if x is None else x.to(DEV)           # noqa: E731
+    q, k, v = (c[n].to(DEV).requires_grad_(True) for n in "qkv")
+    kw = dict(max_q=c["max_q"], max_k=c["max_k"]) if give_max else {}
+    out = ops.seg_attention(q, k, v, t(c["q_ptr"]), t(c["k_ptr"]), c["heads"], c["scale"], score, t(c["q_skip"]), t(c["k_skip"]), **kw)
+    (out * c["coef"].to(out)).sum().backward()
+    return dict(out=out.detach(), dq=q.grad, dk=k.grad, dv=v.grad)
+
+
+def _tags(fn):
+    from dummynode4graphlearning_amd import ops
+    old = ops.kernel_timer
+    ops.kernel_timer = ops.KernelTimer()
+    try:
+        res = fn()
+        return res, set(ops.kernel_timer.summary())
+    finally:
+        ops.kernel_timer = old
+
+
+FUSED_TAGS = {"seg_attn_fwd", "seg_attn_bwd_q", "seg_attn_bwd_kv"}
+_REF = {}
+
+
+def _ref(name, score):
+    if (name, score) not in _REF:
+        c = make_case(name, SEEDS[name])
+        _REF[(name, score)] = (c, reference(c, score))
+    return _REF[(name, score)]
+
+
+def _compare(name, got, ref):
+    bad = []
+    for key in ("out", "dq", "dk", "dv"):
+        terms = ref.get("terms", {}).get(key)
+        if terms is not None and float(ref[key].abs().max()) < 1e-9 * terms:      # zero in exact arithmetic (module docstring)
+            e = float(got[key].abs().max()) / terms
+            print("%s %s |max| / terms %.3e (the reference is zero)" % (name, key, e))
+        else:
+            e = R.rel_max(got[key], ref[key])
+            print("%s %s rel_max %.3e" % (name, key, e))
+        if not e < RTOL:
+            bad.append((key, e))
+    assert not bad, bad
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("score", SCORES)
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_fused_matches_the_float64_restatement(name, score):
+    c, ref = _ref(name, score)
+    assert score == "softmax" or ref["margin"] >= MARGIN, (name, ref["margin"])
+    got, tags = _tags(lambda: run_gpu(c, score))
+    if c["max_k"] > 1024:
+        assert not (tags & FUSED_TAGS), tags                 # above 1024 keys the call takes the composed path by itself
+    else:
+        assert FUSED_TAGS <= tags, tags
+    _compare(name, got, ref)
+    for key in ("out", "dq"):
+        if c["q_skip"] is not None:
+            assert not got[key][c["q_skip"].to(DEV)].any(), key              # a skipped query row is exactly zero
+    for key in ("dk", "dv"):
+        if c["k_skip"] is not None:
+            assert not got[key][c["k_skip"].to(DEV)].any(), key              # a skipped key takes no weight
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("score", SCORES)
+@pytest.mark.parametrize("name", ["mixed", "mixed_block", "skips_block", "k300"])
+def test_two_runs_are_bitwise_equal_and_the_maxima_may_be_left_out(name, score):
+    c, _ = _ref(name, score)
+    a, b, d = run_gpu(c, score), run_gpu(c, score), run_gpu(c, score, give_max=False)
+    for key in a:
+        assert torch.equal(a[key], b[key]), key
+        assert torch.equal(a[key], d[key]), key
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("score", SCORES)
+@pytest.mark.parametrize("name", ["mixed", "skips", "skips_block", "one_live_key", "q65_block"])
+def test_composed_path_agrees_and_shows_no_fused_tag(name, score):
+    from dummynode4graphlearning_amd import ops
+    c, ref = _ref(name, score)
+    assert score == "softmax" or ref["margin"] >= MARGIN
+
+    def composed():
+        with ops.attn_fused(False):
+            return run_gpu(c, score)
+    got, tags = _tags(composed)
+    assert not (tags & FUSED_TAGS), tags
+    _compare(name, got, ref)
+    fused = run_gpu(c, score)
+    for key in ("out", "dq", "dk", "dv"):                    # fused against composed, in units of the reference's magnitude
+        mag = float(ref[key].abs().max())
+        if key in ref["terms"] and mag < 1e-9 * ref["terms"][key]:
+            mag = ref["terms"][key]
+        e = float((got[key].double() - fused[key].double()).abs().max()) / mag
+        print("%s %s fused - composed %.3e" % (name, key, e))
+        assert e < RTOL, (key, e)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float64])
+def test_other_dtypes_take_the_composed_path(dtype):
+    from dummynode4graphlearning_amd import ops
+    c, ref = _ref("spread1", "sparsemax")
+    t = lambda x: None if x is None else x.to(DEV)           # noqa: E731
+
+    def run():
+        return ops.seg_attention(c["q"].to(DEV, dtype), c["k"].to(DEV, dtype), c["v"].to(DEV, dtype), t(c["q_ptr"]), t(c["k_ptr"]),
+                                 c["heads"], c["scale"], "sparsemax", t(c["q_skip"]), t(c["k_skip"]))
+    out, tags = _tags(run)
+    assert out.dtype == dtype and not (tags & FUSED_TAGS)
+    if dtype == torch.float64:
+        assert R.rel_max(out, ref["out"]) < 1e-12
+    else:                                                     # bf16 inputs: compare with the restatement on the rounded inputs
+        cb = dict(c, q=c["q"].bfloat16().float(), k=c["k"].bfloat16().float(), v=c["v"].bfloat16().float())
+        want = reference(cb, "softmax")["out"]
+        got = ops.seg_attention(cb["q"].to(DEV, dtype), cb["k"].to(DEV, dtype), cb["v"].to(DEV, dtype), t(c["q_ptr"]), t(c["k_ptr"]),
+                                c["heads"], c["scale"], "softmax", t(c["q_skip"]), t(c["k_skip"]))
+        # bf16 keeps 8 bits.  |z| < 4 at this spread, so a rounded score is off by at most 2^-7: numerator and denominator of a
+        # weight by 2^-7 each, and the weights and the output are rounded once more (2^-9 each): 2.5 * 2^-7, asserted as 3 * 2^-7
+        assert R.rel_max(got, want) < 3 * 2.0 ** -7
+
+
+@pytest.mark.gpu
+def test_special_score_patterns():
+    from dummynode4graphlearning_amd import ops
+    g = torch.Generator().manual_seed(5)
+    H, heads = 64, 4
+    for klen in (8, 100):                                     # both classes
+        kp = torch.tensor([0, klen], dtype=torch.int32, device=DEV)
+        qp = torch.tensor([0, 1], dtype=torch.int32, device=DEV)
+        k, v = torch.randn(klen, H, generator=g).to(DEV), torch.randn(klen, H, generator=g).to(DEV)
+        # all scores equal: every weight is 1 / klen (|z - tau| = 1 / klen >= MARGIN)
+        out = ops.seg_attention(torch.zeros(1, H, device=DEV), k, v, qp, kp, heads, 0.25)
+        assert R.rel_max(out, v.double().mean(0, keepdim=True)) < RTOL
+        # one score ahead by more than 1: exactly one non-zero weight, and it is 1
+        q = torch.zeros(1, H, device=DEV)
+        k2 = torch.zeros(klen, H, device=DEV)
+        q[0] = 1.0
+        k2[klen // 2] = 1.0                                   # z = 16 * 0.25 = 4 for that key, 0 for the others
+        out = ops.seg_attention(q, k2, v, qp, kp, heads, 0.25)
+        assert torch.equal(out[0], v[klen // 2])
+        # two bit-identical key rows: bit-equal weights (dv_j = p_j dOut with a single query row)
+        k3 = torch.randn(klen, H, generator=g).to(DEV)
+        k3[klen - 1] = k3[1]
+        q3 = (k3[1] * 0.5).view(1, H).contiguous()
+        v3 = v.clone().requires_grad_(True)
+        for score in SCORES:
+            v3.grad = None
+            ops.seg_attention(q3, k3, v3, qp, kp, heads, 0.25, score).sum().backward()
+            assert torch.equal(v3.grad[1], v3.grad[klen - 1]) and v3.grad[1].abs().sum() > 0, score
+
+
+# ------------------------------------------------------------------------------------------------ window pooling
+POOL_PTR = [0, 3, 8, 14, 25, 37, 38]                          # spans: 3 and 4 rows (<= mem_len), 5 (mem_len + 1), 11, 12, 1 row
+
+
+def _pool_case():
+    g = torch.Generator().manual_seed(11)
+    rows = torch.randn(38, 10, generator=g)
+    skip = torch.zeros(38, dtype=torch.bool)
+    skip[[7, 8, 24, 30]] = True                               # last row of pair 1 (span 4), first of pair 2 (span 5), last of pair 3 (11), inside pair 4
+    coef = torch.randn(6 * 4, 10, generator=g)
+    return rows, torch.tensor(POOL_PTR, dtype=torch.int32), skip, coef
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_skip", [True, False])
+@pytest.mark.parametrize("mode", ["mean", "sum", "max"])
+def test_window_pool_matches_the_restatement_both_ways(mode, with_skip):
+    from dummynode4graphlearning_amd import ops
+    rows, ptr, skip, coef = _pool_case()
+    skip = skip if with_skip else None
+    x64 = rows.double().requires_grad_(True)
+    want, want_mask = R.seg_window_pool(x64, ptr, skip, 4, mode)
+    (want * coef.double()).sum().backward()
+    outs = []
+    for fused in (True, False, True):
+        x = rows.to(DEV).requires_grad_(True)
+        with ops.attn_fused(fused):
+            (mem, mask), tags = _tags(lambda: ops.seg_window_pool(x, ptr.to(DEV), None if skip is None else skip.to(DEV), 4, mode))
+        assert ("seg_window_pool" in tags) == fused
+        (mem * coef.to(DEV)).sum().backward()
+        assert torch.equal(mask.cpu(), want_mask)
+        assert R.rel_max(mem, want) < RTOL and R.rel_max(x.grad, x64.grad) < RTOL, (mode, fused)
+        outs.append((mem.detach(), x.grad))
+    assert torch.equal(outs[0][0], outs[2][0]) and torch.equal(outs[0][1], outs[2][1])
+
+
+def find_seeds(limit=400):
+    """CPU: the first seed per case whose float64 sparsemax margin is at least MARGIN."""
+    for name in CASES:
+        for seed in range(limit):
+            if reference(make_case(name, seed), "sparsemax")["margin"] >= MARGIN:
+                print('"%s": %d,' % (name, seed), flush=True)
+                break
+        else:
+            print("%s: no seed below %d" % (name, limit), flush=True)
+
+
+if __name__ == "__main__":
+    find_seeds()
