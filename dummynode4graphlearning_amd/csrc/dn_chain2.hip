@@ -37,11 +37,6 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kH = 256;
 constexpr int kRowB = 2 * kH;                 // bytes per row
 constexpr int kTR = 32;                       // rows per tile
@@ -56,13 +51,6 @@ constexpr int kDma = 2, kStores = 4;          // vector-memory operations every 
 __device__ __attribute__((aligned(16))) uint4 g_c2_zero[64];       // 1 KiB of zeros: what rows past the end read
 __device__ __attribute__((aligned(16))) uint4 g_c2_dump[64 * 8];   // where their results go (1 KiB per wave, never read)
 
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-    typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (bf16_t)a;
-    v[1] = (bf16_t)b;
-    return __builtin_bit_cast(uint32_t, v);
-}
 __device__ __forceinline__ uint32_t pos_bits(const u32x4& v) {     // bit i: bf16 element i > 0 (sign clear, magnitude non-zero)
     uint32_t bits = 0;
 #pragma unroll
@@ -89,8 +77,6 @@ __device__ __forceinline__ void c2_wait(int t) {                          // AHE
 }
 static_assert(kD == 4, "c2_wait spells out the first kD iterations");
 
-#define DN_C2_READ128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
-
 template <bool KEEP, bool SBITS>
 __global__ __launch_bounds__(kThreads) void rows_chain2_ring_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1n, const bf16_t* __restrict__ b1, const bf16_t* __restrict__ W2n,
@@ -98,8 +84,7 @@ __global__ __launch_bounds__(kThreads) void rows_chain2_ring_kernel(
     int32_t num_tiles, bf16_t* __restrict__ Y1, bf16_t* __restrict__ Y2, uint8_t* __restrict__ bits1, uint8_t* __restrict__ bits2,
     float slope) {
     __shared__ __attribute__((aligned(1024))) char lds[kNS * kStageB + 2 * kTileB + 4 * kBitsB];
-    typedef __attribute__((address_space(3))) char* lds_wp;
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_wp)lds;
+    const unsigned lds_base = lds_addr(lds);
     constexpr unsigned kH1Off = kNS * kStageB;                            // the two hand-off tiles (layer 1 -> layer 2)
     constexpr unsigned kObOff = kH1Off + 2 * kTileB;                      // sign-bit tiles [layer][2]
     static_assert(kStageB % 1024 == 0 && kH1Off % 1024 == 0, "the fragment addressing XORs bits 6-7 of a stage-relative offset");
@@ -123,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void rows_chain2_ring_kernel(
         char* scr = lds + kH1Off + wave * 2048;                           // (the hand-off tiles are idle until the first barrier)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            dn_bf16x8 tmp[8][2];
+            bf16x8 tmp[8][2];
             dn_load_w_kn32<8>(Wn, kH, c0 + 32 * h, lane, scr, tmp);
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks)
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(kThreads) void rows_chain2_ring_kernel(
                 const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe(kb, 2 * i, 1), m1 = (uint32_t)__builtin_amdgcn_sbfe(kb, 2 * i + 1, 1);
                 const uint32_t mk = (m0 & 0xffffu) | (m1 & 0xffff0000u);
                 uint32_t alt = 0u;
-                if (slope != 0.f) alt = pack2(__uint_as_float(v[i] << 16) * slope, __uint_as_float(v[i] & 0xffff0000u) * slope);
+                if (slope != 0.f) alt = pack_bf16x2(__uint_as_float(v[i] << 16) * slope, __uint_as_float(v[i] & 0xffff0000u) * slope);
                 v[i] = (v[i] & mk) | (alt & ~mk);
             }
             *pp = v;
@@ -212,11 +197,11 @@ __global__ __launch_bounds__(kThreads) void rows_chain2_ring_kernel(
     {                                                                                                                 \
         const unsigned a_ = (sb + off0) ^ (unsigned)(((KS) & 3) << 6);                                                \
         if ((KS) < 4) {                                                                                               \
-            DN_C2_READ128(xf[SLOT][0], a_, 0);                                                                        \
-            DN_C2_READ128(xf[SLOT][1], a_, 8192);                                                                     \
+            DN_DS_READ128(xf[SLOT][0], a_, 0);                                                                        \
+            DN_DS_READ128(xf[SLOT][1], a_, 8192);                                                                     \
         } else {                                                                                                      \
-            DN_C2_READ128(xf[SLOT][0], a_, 256);                                                                      \
-            DN_C2_READ128(xf[SLOT][1], a_, 8448);                                                                     \
+            DN_DS_READ128(xf[SLOT][0], a_, 256);                                                                      \
+            DN_DS_READ128(xf[SLOT][1], a_, 8448);                                                                     \
         }                                                                                                             \
     }
 #define DN_C2_MFMA8(SLOT, KS)                                                                                             \
@@ -309,7 +294,7 @@ __global__ __launch_bounds__(kThreads) void rows_chain2_ring_kernel(
                 }
                 u32x4 o;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = pack2(v[2 * i], v[2 * i + 1]);
+                for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
                 if constexpr (SBITS) {
                     // element > 0 <=> its fp32 pattern is a positive integer (a NaN with a clear sign included, as for the stored
                     // bf16; a positive fp32 rounds to a positive bf16 or to +0 only below 2^-134, which no activation reaches)

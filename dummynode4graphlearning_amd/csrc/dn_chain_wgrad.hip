@@ -25,8 +25,6 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
-
 constexpr int kH = 256;
 constexpr int kTile = 64;                      // output tile of a workgroup (256 threads: 4 x 4 outputs each)
 constexpr int kKC = 32;                        // K chunk

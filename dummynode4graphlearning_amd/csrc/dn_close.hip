@@ -39,13 +39,6 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef short short8v __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct Unit {
     int32_t flags, beg, end, aux;      // X unit: nodes [beg, end), aux = tile;  ENTRY unit: entries [beg, end), aux = the tile's first node
 };                                     // AGG unit: the workgroup's tiles number [beg, end) (their segments' aux rows); NOP: nothing
@@ -488,16 +481,6 @@ __device__ int32_t g_close_zero[64];                // zeros (device globals are
 __device__ unsigned long long g_close_times[256][3];
 #endif
 
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-    typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (bf16_t)a;
-    v[1] = (bf16_t)b;
-    return __builtin_bit_cast(uint32_t, v);
-}
-
-#define DN_DS_READ128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
-
 // FOLD: 0 none; 1 the per-(segment, tile) column sums of x leave as fp32 partial rows (seg_part; dn_fold_tail_bf16 finishes);
 // 2 every segment lies inside one tile: its column sum leaves as the bf16 aux row, and the workgroup's AGG units at the end of
 // its stream multiply those rows by W_agg and add each product to its output row (agg_idx) -- no partial rows, no tail launch.
@@ -516,9 +499,8 @@ __global__ __launch_bounds__(kThreads) void rows_close_ring_kernel(
     __shared__ __attribute__((aligned(256))) int32_t idxR[kLoaders][kIdxRing][kRowsPerLoader]; // ... and source rows
     __shared__ __attribute__((aligned(16))) char wscr[kCompute][2048];                         // transposition scratch of a [k][n] W
     __shared__ __attribute__((aligned(16))) float segL[FOLD == 2 ? kCompute : 1][4][8];       // running column sums of a multi-tile graph
-    typedef __attribute__((address_space(3))) char* lds_wp;
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_wp)lds;
-    const unsigned desc_base = (unsigned)(uintptr_t)(lds_wp)&descL[0][0];
+    const unsigned lds_base = lds_addr(lds);
+    const unsigned desc_base = lds_addr(&descL[0][0]);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wg = (int)blockIdx.x, nwg = (int)gridDim.x;
@@ -542,10 +524,10 @@ __global__ __launch_bounds__(kThreads) void rows_close_ring_kernel(
             const int rl = kRowsPerLoader * q + 2 * j + rin;               // row of the stage this lane fills
             swoff[j] = (pos ^ (rl & 15)) * 16;                             // source byte offset inside the row
         }
-        const unsigned rec_base = (unsigned)(uintptr_t)(lds_wp)&recR[q][0][0];
-        const unsigned idx_base = (unsigned)(uintptr_t)(lds_wp)&idxR[q][0][0];
-        const unsigned mask_base = (unsigned)(uintptr_t)(lds_wp)&maskR[0][0];
-        const unsigned fold_base = (unsigned)(uintptr_t)(lds_wp)&foldR[0][0];
+        const unsigned rec_base = lds_addr(&recR[q][0][0]);
+        const unsigned idx_base = lds_addr(&idxR[q][0][0]);
+        const unsigned mask_base = lds_addr(&maskR[0][0]);
+        const unsigned fold_base = lds_addr(&foldR[0][0]);
         const int myrow = 2 * (lane & 3) + ((lane >> 2) & 1);              // the index ring holds a unit's 8 rows as {0,2,4,6,1,3,5,7}
         // source bases as one base + differences: a three-way select of captured variables makes hipcc keep the closure on the stack
         const uint64_t baseX = (uint64_t)(uintptr_t)X, dS = (uint64_t)(uintptr_t)S - baseX, dA = (uint64_t)(uintptr_t)aux - baseX;
@@ -602,7 +584,6 @@ __global__ __launch_bounds__(kThreads) void rows_close_ring_kernel(
         const char* srcA[kDmaPerTile];
         const char* srcB[kDmaPerTile];
         auto prep = [&](int u, const char* (&src)[kDmaPerTile]) __attribute__((always_inline)) {
-            typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
             const i32x4 iv = *reinterpret_cast<const i32x4*>(&idxR[q][u % kIdxRing][4 * rin]);   // rows rin, 2 + rin, 4 + rin, 6 + rin
             const int kind = recR[q][u % kRecRing][0];
             const bool ent = (kind & kUnitEntry) != 0, agg = FOLD == 2 && (kind & kUnitAgg) != 0;
@@ -980,7 +961,6 @@ __global__ __launch_bounds__(kThreads) void rows_close_ring_kernel(
 #undef DN_FETCH
 #undef DN_KSTEP
 }
-#undef DN_DS_READ128
 
 }  // namespace
 

@@ -90,129 +90,106 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// ---- The preamble of the matrix-core (MFMA) files: vector types, the packed bf16 pair, the transposed LDS fragment read, the
+// 128-bit LDS read, LDS addresses, the row-range record and the fp32 / bf16 element converters -- each defined here only.
+typedef __bf16 bf16_t;
+typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
+typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
+typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
+typedef short short4v __attribute__((ext_vector_type(4)));
+typedef short short8v __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+
+struct Chunk {                                     // rows [beg, end) of relation rel: a chunk of a weight gradient, a tile of a transform
+    int32_t rel, beg, end, pad;
+};
+
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {     // a in the low half
+    bf16x2 v;
+    v[0] = (bf16_t)a;
+    v[1] = (bf16_t)b;
+    return __builtin_bit_cast(uint32_t, v);
+}
+
+// fragment of a K-strided bf16 operand held row-major in LDS (ds_read_b64_tr_b16, the hardware transpose read):
+// element j of lane l = tile[8*(l>>4) + j][col0 + (l&15)]
+__device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int stride, int col0, int lane) {
+    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
+    const bf16_t* a0 = tile + (8 * g + q) * stride + col0 + 4 * p;
+    typedef short4v __attribute__((address_space(3))) * lds_p;
+    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0));
+    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0 + 4 * stride));
+    const short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, f);
+}
+
+#define DN_DS_READ128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
+
+__device__ __forceinline__ unsigned lds_addr(const void* p) {      // the 32-bit LDS address of a __shared__ object
+    return (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)p;
+}
+
+__device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; }
+__device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return (float)p[i]; }
+template <typename T> __device__ __forceinline__ T st(float x) { return (T)x; }
+
 // A wave's slice of a weight matrix stored [k][n] (the layout of the reference's parameters) as MFMA A-operand fragments, which
 // want 8 consecutive k per lane: one 32-k-row slab at a time goes global -> registers (coalesced 16-byte pieces, all slabs
 // requested up front) -> a wave-private LDS scratch -> ds_read_b64_tr_b16 (the hardware transpose).  2-byte gathers instead
 // cost ~30 us per call: hipcc serialises the 128 partial-register loads of a wave behind vmcnt(0) waits.
-//   NC = 32: the wave owns columns n0 .. n0+31, fragment [ks][n] row i <-> column n0 + 8 (i >> 2) + 4 n + (i & 3)  (ring kernels)
+//   NC = 32: the wave owns columns n0 .. n0+31, fragment [ks][n] row i <-> column n0 + 8 (i >> 2) + 4 n + (i & 3)  (ring kernels);
+//            PLAIN: the column order of the dense-row kernels, row i <-> column n0 + 16 n + i
 //   NC = 16: columns n0 .. n0+15, fragment [ks] row i <-> column n0 + i
 // scratch: 32 x 2 NC bytes, 16-byte aligned, private to the wave.  KS = K / 32.
-typedef short dn_short4v __attribute__((ext_vector_type(4)));
-typedef short dn_short8v __attribute__((ext_vector_type(8)));
-typedef __bf16 dn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int dn_u32x4 __attribute__((ext_vector_type(4)));
-
-template <int KS>
-__device__ __forceinline__ void dn_load_w_kn32(const __bf16* __restrict__ w, int ldw, int n0, int lane, char* scratch,
-                                               dn_bf16x8 (&wf)[KS][2]) {
-    typedef dn_short4v __attribute__((address_space(3))) * lds_tr;
+template <int KS, bool PLAIN = false>
+__device__ __forceinline__ void dn_load_w_kn32(const bf16_t* __restrict__ w, int ldw, int n0, int lane, char* scratch,
+                                               bf16x8 (&wf)[KS][2]) {
+    typedef short4v __attribute__((address_space(3))) * lds_tr;
     const int r16 = lane >> 2, pc4 = lane & 3;
-    dn_u32x4 raw[KS][2];
+    u32x4 raw[KS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int h = 0; h < 2; ++h)
-            raw[ks][h] = *reinterpret_cast<const dn_u32x4*>(w + (size_t)(32 * ks + 16 * h + r16) * ldw + n0 + 8 * pc4);
+            raw[ks][h] = *reinterpret_cast<const u32x4*>(w + (size_t)(32 * ks + 16 * h + r16) * ldw + n0 + 8 * pc4);
     const int g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        *reinterpret_cast<dn_u32x4*>(scratch + r16 * 64 + 16 * pc4) = raw[ks][0];
-        *reinterpret_cast<dn_u32x4*>(scratch + (16 + r16) * 64 + 16 * pc4) = raw[ks][1];
+        *reinterpret_cast<u32x4*>(scratch + r16 * 64 + 16 * pc4) = raw[ks][0];
+        *reinterpret_cast<u32x4*>(scratch + (16 + r16) * 64 + 16 * pc4) = raw[ks][1];
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-            const char* a0 = scratch + (8 * g + q4) * 64 + 16 * p4 + 8 * n;
-            const dn_short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0));
-            const dn_short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0 + 4 * 64));
-            const dn_short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            wf[ks][n] = __builtin_bit_cast(dn_bf16x8, f);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// (the same, KC k-slabs per round trip instead of all KS at once: 8 KC staging registers instead of 8 KS -- for a reload in
-//  the middle of a kernel that has no registers to spare; KS / KC dependent round trips)
-template <int KS, int KC>
-__device__ __forceinline__ void dn_load_w_kn32_lean(const __bf16* __restrict__ w, int ldw, int n0, int lane, char* scratch,
-                                                    dn_bf16x8 (&wf)[KS][2]) {
-    typedef dn_short4v __attribute__((address_space(3))) * lds_tr;
-    const int r16 = lane >> 2, pc4 = lane & 3;
-    const int g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
-#pragma unroll
-    for (int k0 = 0; k0 < KS; k0 += KC) {
-        dn_u32x4 raw[KC][2];
-#pragma unroll
-        for (int kk = 0; kk < KC; ++kk)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                raw[kk][h] = *reinterpret_cast<const dn_u32x4*>(w + (size_t)(32 * (k0 + kk) + 16 * h + r16) * ldw + n0 + 8 * pc4);
-#pragma unroll
-        for (int kk = 0; kk < KC; ++kk) {
-            *reinterpret_cast<dn_u32x4*>(scratch + r16 * 64 + 16 * pc4) = raw[kk][0];
-            *reinterpret_cast<dn_u32x4*>(scratch + (16 + r16) * 64 + 16 * pc4) = raw[kk][1];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const char* a0 = scratch + (8 * g + q4) * 64 + 16 * p4 + 8 * n;
-                const dn_short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0));
-                const dn_short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0 + 4 * 64));
-                const dn_short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                wf[k0 + kk][n] = __builtin_bit_cast(dn_bf16x8, f);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-}
-
-// (the same with the PLAIN column order of the dense-row kernels: fragment [ks][n] row i <-> column n0 + 16 n + i)
-template <int KS>
-__device__ __forceinline__ void dn_load_w_kn32p(const __bf16* __restrict__ w, int ldw, int n0, int lane, char* scratch,
-                                                dn_bf16x8 (&wf)[KS][2]) {
-    typedef dn_short4v __attribute__((address_space(3))) * lds_tr;
-    const int r16 = lane >> 2, pc4 = lane & 3;
-    dn_u32x4 raw[KS][2];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            raw[ks][h] = *reinterpret_cast<const dn_u32x4*>(w + (size_t)(32 * ks + 16 * h + r16) * ldw + n0 + 8 * pc4);
-    const int g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        *reinterpret_cast<dn_u32x4*>(scratch + r16 * 64 + 16 * pc4) = raw[ks][0];
-        *reinterpret_cast<dn_u32x4*>(scratch + (16 + r16) * 64 + 16 * pc4) = raw[ks][1];
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            const char* a0 = scratch + (8 * g + q4) * 64 + 32 * n + 8 * p4;
-            const dn_short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0));
-            const dn_short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0 + 4 * 64));
-            const dn_short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            wf[ks][n] = __builtin_bit_cast(dn_bf16x8, f);
+            const char* a0 = PLAIN ? scratch + (8 * g + q4) * 64 + 32 * n + 8 * p4 : scratch + (8 * g + q4) * 64 + 16 * p4 + 8 * n;
+            const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0));
+            const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0 + 4 * 64));
+            const short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            wf[ks][n] = __builtin_bit_cast(bf16x8, f);
         }
         __builtin_amdgcn_wave_barrier();
     }
 }
 
 template <int KS>
-__device__ __forceinline__ void dn_load_w_kn16(const __bf16* __restrict__ w, int ldw, int n0, int lane, char* scratch,
-                                               dn_bf16x8 (&wf)[KS]) {
-    typedef dn_short4v __attribute__((address_space(3))) * lds_tr;
+__device__ __forceinline__ void dn_load_w_kn16(const bf16_t* __restrict__ w, int ldw, int n0, int lane, char* scratch,
+                                               bf16x8 (&wf)[KS]) {
+    typedef short4v __attribute__((address_space(3))) * lds_tr;
     const int r32 = lane >> 1, pc2 = lane & 1;
-    dn_u32x4 raw[KS];
+    u32x4 raw[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) raw[ks] = *reinterpret_cast<const dn_u32x4*>(w + (size_t)(32 * ks + r32) * ldw + n0 + 8 * pc2);
+    for (int ks = 0; ks < KS; ++ks) raw[ks] = *reinterpret_cast<const u32x4*>(w + (size_t)(32 * ks + r32) * ldw + n0 + 8 * pc2);
     const int g = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        *reinterpret_cast<dn_u32x4*>(scratch + r32 * 32 + 16 * pc2) = raw[ks];
+        *reinterpret_cast<u32x4*>(scratch + r32 * 32 + 16 * pc2) = raw[ks];
         __builtin_amdgcn_wave_barrier();
         const char* a0 = scratch + (8 * g + q4) * 32 + 8 * p4;
-        const dn_short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0));
-        const dn_short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0 + 4 * 32));
-        const dn_short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        wf[ks] = __builtin_bit_cast(dn_bf16x8, f);
+        const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0));
+        const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0 + 4 * 32));
+        const short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        wf[ks] = __builtin_bit_cast(bf16x8, f);
         __builtin_amdgcn_wave_barrier();
     }
 }

@@ -29,10 +29,6 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32;
 
 constexpr int kH = 64, kWaves = kH / 16, kThreads = 64 * kWaves;
@@ -40,14 +36,6 @@ constexpr int kMaxNodes = 64;          // nodes of a graph (4 node blocks of 16)
 constexpr int kMaxEdges = 1024;        // edges of a graph
 constexpr int kRowB = 2 * kH;          // 128 bytes per row
 constexpr int kZeroRow = kMaxNodes;    // row 64 of the image: zeros (the input row of a null edge)
-
-__device__ __forceinline__ u32 pack2(float a, float b) {
-    typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (bf16_t)a;
-    v[1] = (bf16_t)b;
-    return __builtin_bit_cast(u32, v);
-}
 
 struct GraphLds {
     __attribute__((aligned(16))) char x[(kMaxNodes + 1) * kRowB];          // the conv's input rows + the zero row, swizzled
@@ -129,7 +117,7 @@ __global__ __launch_bounds__(kThreads, RB <= 8 ? 2 : 1) void conv_graphs_kernel(
     constexpr int NM = RB + 1 + (MODE != 0 ? 2 : 0);
     bf16x8 wf[NM][2];
     {
-        typedef dn_short4v __attribute__((address_space(3))) * lds_tr;
+        typedef short4v __attribute__((address_space(3))) * lds_tr;
         const int r32 = lane >> 1, pc2 = lane & 1;
         const int q4 = j >> 2, p4 = j & 3;
         char* scratch = L.wscr[wave];
@@ -160,9 +148,9 @@ __global__ __launch_bounds__(kThreads, RB <= 8 ? 2 : 1) void conv_graphs_kernel(
                     *reinterpret_cast<u32x4*>(scratch + r32 * 32 + 16 * pc2) = rawv[q][ks];   // (dn_load_w_kn16's transpose: 32 k x 16 n)
                     __builtin_amdgcn_wave_barrier();
                     const char* a0 = scratch + (8 * g + q4) * 32 + 8 * p4;
-                    const dn_short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0));
-                    const dn_short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0 + 4 * 32));
-                    const dn_short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0));
+                    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(a0 + 4 * 32));
+                    const short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                     wf[mi][ks] = __builtin_bit_cast(bf16x8, f);
                     __builtin_amdgcn_wave_barrier();
                 }
@@ -336,7 +324,7 @@ __global__ __launch_bounds__(kThreads, RB <= 8 ? 2 : 1) void conv_graphs_kernel(
                 }
                 // lane (column j, group g) now holds P[blk + 4 g + i][j] (p1) and P[blk + 16 + 4 g + i][j] (p2): exactly the B
                 // fragment of a product over 32 edge SLOTS, slot 8 g + t <-> edge 4 g + t (t < 4) / 16 + 4 g + t - 4
-                const u32x4 pw = {pack2(p1[0], p1[1]), pack2(p1[2], p1[3]), pack2(p2[0], p2[1]), pack2(p2[2], p2[3])};
+                const u32x4 pw = {pack_bf16x2(p1[0], p1[1]), pack_bf16x2(p1[2], p1[3]), pack_bf16x2(p2[0], p2[1]), pack_bf16x2(p2[2], p2[3])};
                 const bf16x8 pb = __builtin_bit_cast(bf16x8, pw);
                 const u32 d1 = *reinterpret_cast<const u32*>(&L.e_out[blk + 4 * g]);         // out nodes of my 8 slots
                 const u32 d2 = *reinterpret_cast<const u32*>(&L.e_out[blk + 16 + 4 * g]);

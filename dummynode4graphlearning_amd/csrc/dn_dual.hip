@@ -17,12 +17,6 @@ constexpr int kBlock = 256;
 constexpr int kMaxH = 256;
 constexpr int kMaxGrid = 4096;
 
-typedef __bf16 bf16_t;
-
-__device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ T st(float x) { return (T)x; }
-
 enum { kModeEdge = DN_DUAL_EDGE, kModeSub = DN_DUAL_SUB, kModeMult = DN_DUAL_MULT };
 
 // scale_e * m_e of edge e at column col (0 for an edge id or a source outside the tables: never read out of bounds)

@@ -15,7 +15,6 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
 struct Piece { int32_t rel, beg, end, pad; };
 
 constexpr int TM = 64, TN = 64, TK = 16, kThreads = 256;
@@ -80,7 +79,6 @@ __global__ __launch_bounds__(kThreads) void rows_gemm_kernel(const T* __restrict
 // per 64 x 64 output tile: wave w owns rows 16 w .. 16 w + 15 of the tile and all 64 columns (4 accumulators); the TRANSPOSED
 // product is formed (A operand = 16 columns of the weight, B operand = the wave's 16 rows), so a lane ends up with 4 consecutive
 // columns of one row = one 16-byte store.  Operands are staged through LDS in K-steps of 32 (zero-padded at the edges).
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // KC: columns of k per step.  A step is a dependent chain (loads -> LDS -> barrier -> a few MFMAs -> barrier), so its cost is the
 // loads' latency whatever KC is: K >= 128 takes steps of 128 (a 256-wide readout Linear on 16 k rows: eight round trips -> two).
 template <int KC>
@@ -97,9 +95,9 @@ __global__ __launch_bounds__(kThreads) void rows_gemm_mfma_f32_kernel(const floa
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, g = lane >> 4;
     const float* Wr = W + (size_t)tl.rel * K * N;
-    f32x4_t acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 4; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < K; k0 += KC) {
         for (int i = tid; i < TM * KC; i += kThreads) {                  // A tile: consecutive threads along k (contiguous in memory)
             const int r = i / KC, k = i % KC;

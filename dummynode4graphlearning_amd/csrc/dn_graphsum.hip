@@ -15,27 +15,9 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef short short8v __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kGtRows = 64;        // rows of a tile
 constexpr int gt_threads(int H) { return H >= 128 ? 512 : 256; }   // 8 waves measured best at H = 128 (4: -10 %, 16: -12 %)
 constexpr int kGtPad = 8;          // bf16 elements of row padding (planes and adjacency)
-
-// element j of lane l = tile[8 * (l >> 4) + j][col0 + (l & 15)]   (hardware transpose read, as in dn_rel.hip)
-__device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int stride, int col0, int lane) {
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const bf16_t* a0 = tile + (8 * g + q) * stride + col0 + 4 * p;
-    typedef short4v __attribute__((address_space(3))) * lds_p;
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0));
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0 + 4 * stride));
-    const short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, f);
-}
 
 // One persistent workgroup walks tiles blockIdx.x, + gridDim.x, ...; what the NEXT tile needs from memory (its rows, its list
 // bounds, its index entries) is requested right after this tile's rows have been handed to LDS and lands under this tile's
@@ -221,8 +203,8 @@ __global__ __launch_bounds__(gt_threads(H)) void graph_tile_sum_kernel(const flo
                 float4 o;
                 o.x = fmaf(self_coef, cur.xr[k].x, d.x); o.y = fmaf(self_coef, cur.xr[k].y, d.y);
                 o.z = fmaf(self_coef, cur.xr[k].z, d.z); o.w = fmaf(self_coef, cur.xr[k].w, d.w);
-                typedef float f32x4v __attribute__((ext_vector_type(4)));   // streaming store (the tile's rows are done: -6 % launch time)
-                __builtin_nontemporal_store(f32x4v{o.x, o.y, o.z, o.w}, reinterpret_cast<f32x4v*>(out + (size_t)(row_beg + r) * H + c4 * 4));
+                // streaming store (the tile's rows are done: -6 % launch time)
+                __builtin_nontemporal_store(f32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<f32x4*>(out + (size_t)(row_beg + r) * H + c4 * 4));
             }
         }
         __syncthreads();                                                   // outL (the planes) is rewritten by the next tile
@@ -287,10 +269,10 @@ __global__ __launch_bounds__(256) void gather_rows_sum_kernel(const float* __res
             if (group != 0) continue;
         }
         const float4 xs = *reinterpret_cast<const float4*>(x + (size_t)s * H + lane * 4);
-        typedef float f32x4v __attribute__((ext_vector_type(4)));           // streaming store: the row is re-read by a later launch only
-        __builtin_nontemporal_store(f32x4v{fmaf(self_coef, xs.x, acc[0]), fmaf(self_coef, xs.y, acc[1]), fmaf(self_coef, xs.z, acc[2]),
-                                           fmaf(self_coef, xs.w, acc[3])},
-                                    reinterpret_cast<f32x4v*>(out + (size_t)s * H + lane * 4));
+        // streaming store: the row is re-read by a later launch only
+        __builtin_nontemporal_store(f32x4{fmaf(self_coef, xs.x, acc[0]), fmaf(self_coef, xs.y, acc[1]), fmaf(self_coef, xs.z, acc[2]),
+                                          fmaf(self_coef, xs.w, acc[3])},
+                                    reinterpret_cast<f32x4*>(out + (size_t)s * H + lane * 4));
     }
 }
 

@@ -35,17 +35,6 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef short short8v __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-struct Chunk {
-    int32_t rel, beg, end, pad;
-};
-
 constexpr int kH = 256;
 constexpr int kRowB = 2 * kH;                  // bytes per row
 constexpr int kTR = 32;                        // rows per tile
@@ -62,14 +51,6 @@ __device__ __attribute__((aligned(16))) uint4 g_mb_dump[64 * 8];    // where the
 
 __device__ __forceinline__ int swz(int r) {    // s(r) of the header
     return ((r >> 2) & 1) | ((r & 3) << 1) | ((((r >> 3) ^ (r >> 2)) & 1) << 3);
-}
-
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-    typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (bf16_t)a;
-    v[1] = (bf16_t)b;
-    return __builtin_bit_cast(uint32_t, v);
 }
 
 // "tile t has landed" (MASKED: and the G rows + bits of tile t + 1) at the top of iteration t.  Issue order of a wave: tiles 0..2
@@ -102,7 +83,6 @@ __device__ __forceinline__ bf16x8 frag_val(const Frag& f) {
         asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"((fr).lo) : "v"(ad));                                          \
         asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "=v"((fr).hi) : "v"(ad2));                             \
     } while (0)
-#define DN_MB_READ128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
 static_assert(4 * kRowB == 2048, "offset of a transposed fragment's second half");
 
 template <bool MASKED>
@@ -114,8 +94,7 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
                                                                  float* __restrict__ colsum_partial, bf16_t* __restrict__ Gn,
                                                                  float slope) {
     __shared__ __attribute__((aligned(1024))) char lds[kNST * kStB];
-    typedef __attribute__((address_space(3))) char* lds_wp;
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_wp)lds;
+    const unsigned lds_base = lds_addr(lds);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const Chunk ch = chunks[blockIdx.x];
@@ -205,7 +184,7 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
                 const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe(kb, 2 * i, 1), m1 = (uint32_t)__builtin_amdgcn_sbfe(kb, 2 * i + 1, 1);
                 const uint32_t mk = (m0 & 0xffffu) | (m1 & 0xffff0000u);
                 uint32_t alt = 0u;
-                if (slope != 0.f) alt = pack2(__uint_as_float(v[i] << 16) * slope, __uint_as_float(v[i] & 0xffff0000u) * slope);
+                if (slope != 0.f) alt = pack_bf16x2(__uint_as_float(v[i] << 16) * slope, __uint_as_float(v[i] & 0xffff0000u) * slope);
                 v[i] = (v[i] & mk) | (alt & ~mk);
             }
             *pp = v;
@@ -243,9 +222,9 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
     {                                                                                                                 \
         const unsigned a_ = (sg + off0) ^ (unsigned)(((KS) & 3) << 6);                                                \
         if ((HH) == 0) {                                                                                              \
-            if ((KS) < 4) { DN_MB_READ128(xf[SLOT], a_, 0); } else { DN_MB_READ128(xf[SLOT], a_, 256); }              \
+            if ((KS) < 4) { DN_DS_READ128(xf[SLOT], a_, 0); } else { DN_DS_READ128(xf[SLOT], a_, 256); }              \
         } else {                                                                                                      \
-            if ((KS) < 4) { DN_MB_READ128(xf[SLOT], a_, 8192); } else { DN_MB_READ128(xf[SLOT], a_, 8448); }          \
+            if ((KS) < 4) { DN_DS_READ128(xf[SLOT], a_, 8192); } else { DN_DS_READ128(xf[SLOT], a_, 8448); }          \
         }                                                                                                             \
     }
 #define DN_MB_MFMA2(SLOT, KS)                                                                                         \
@@ -287,7 +266,7 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
             }                                                                                                         \
         }                                                                                                             \
         u32x4 o;                                                                                                      \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) o[i] = pack2(v[2 * i], v[2 * i + 1]);                            \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);                      \
         char* dst = p < (int64_t)cend ? reinterpret_cast<char*>(Gn) + (uint64_t)p * kRowB + ycol : dump;              \
         __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(dst)); /* (always issued: the DMA waits count it) */  \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
@@ -380,7 +359,6 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
     }
 }
 #undef DN_MB_TR
-#undef DN_MB_READ128
 
 }  // namespace
 

@@ -16,7 +16,6 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
 constexpr int kBlock = 256;
 constexpr int kChunkRows = 64;
 
@@ -35,7 +34,6 @@ template <> struct V4<bf16_t> {
         v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
     }
     static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[4]) {
-        typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
         bf16x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = (bf16_t)v[i];

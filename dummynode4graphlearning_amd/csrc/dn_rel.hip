@@ -16,36 +16,15 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef short short8v __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kWgThreads = 512;  // 8 waves: 2 (rows of the output tile) x 4 (columns)
 constexpr int kTileRows = 64;    // rows staged per iteration (two MFMA 16x16x32 K-steps)
 constexpr int kPad = 8;          // bf16 elements of row padding in LDS
-
-struct Chunk {
-    int32_t rel, beg, end, pad;
-};
 
 // colsum_of as the C entry takes it: operand (0 none, 1 A, 2 G) | (relation + 1) << 8 -- column sums of ONE relation's rows only
 // (0 in bits 8..: of every relation's).  What a chunk of relation `rel` has to sum: the operand, or nothing (its sums are zeros).
 __device__ __forceinline__ int32_t colsum_for(int32_t colsum_arg, int32_t rel) {
     const int32_t only = colsum_arg >> 8;
     return (only == 0 || rel + 1 == only) ? (colsum_arg & 0xff) : 0;
-}
-
-__device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int stride, int col0, int lane) {
-    // fragment of a K-strided operand: element j of lane l = tile[8*(l>>4) + j][col0 + (l&15)]
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const bf16_t* a0 = tile + (8 * g + q) * stride + col0 + 4 * p;
-    typedef short4v __attribute__((address_space(3))) * lds_p;
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0));
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0 + 4 * stride));
-    const short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, f);
 }
 
 __device__ __forceinline__ uint4 keep_bits(const uint4& v, uint32_t bits) {     // bit i of `bits` <-> bf16 element i of v
@@ -322,7 +301,7 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_dma_kernel(const bf16_t
     constexpr int GL = 2 * PPW;                    // DMA instructions per wave and tile (+ 1 on the wave that fetches a tile's mask bits)
     constexpr int MT = H / 2 / 16, NT = H / 4 / 16;
     __shared__ __attribute__((aligned(1024))) char lds[NST * STB];
-    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
+    const unsigned lds_base = lds_addr(lds);
 
     const Chunk ch = chunks[blockIdx.x];
     const int32_t colsum_all = colsum_arg & 0xff, colsum_of = colsum_for(colsum_arg, ch.rel);   // (a chunk of another relation: zeros)
@@ -593,8 +572,7 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_ix_kernel(const bf16_t*
     constexpr int kOps = 5;                        // vector-memory operations a wave issues per tile
     __shared__ __attribute__((aligned(1024))) char lds[NST * STB];
     __shared__ __attribute__((aligned(32))) int32_t idxL[8][kSlots][8];       // {ia[p0..p0+3], ig[p0..p0+3]} of a wave's rows
-    typedef __attribute__((address_space(3))) char* lds_wp;
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_wp)lds;
+    const unsigned lds_base = lds_addr(lds);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
@@ -603,7 +581,7 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_ix_kernel(const bf16_t*
     const int ntiles = (ch.end - ch.beg + TR - 1) / TR;
     const int32_t ch_beg = ch.beg, ch_end = ch.end;
     const char* zero = reinterpret_cast<const char*>(g_zero_row);
-    const unsigned idx_base = (unsigned)(uintptr_t)(lds_wp)&idxL[wave][0][0];
+    const unsigned idx_base = lds_addr(&idxL[wave][0][0]);
 
     // {first row of my 4, last row of the tile, live} of tile T (wave-uniform values; tiles past the end repeat the last one)
     auto tile_rows = [&](int T, int& p0, int& pe, bool& live) {
@@ -641,7 +619,6 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_ix_kernel(const bf16_t*
         int p0, pe;
         bool live;
         tile_rows(T, p0, pe, live);
-        typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
         const i32x4 iv = *reinterpret_cast<const i32x4*>(&idxL[wave][T % kSlots][4 * rin]);   // {ia[k], ia[2 + k], ig[k], ig[2 + k]}, k = rin
         const unsigned st = lds_base + (unsigned)(T % NST) * STB;
 #pragma unroll
@@ -840,8 +817,7 @@ __device__ __forceinline__ void wgrad_ls_body(const bf16_t* __restrict__ A, cons
     constexpr int MT = H / 2 / 16, NT = H / 4 / 16;
     constexpr int kSlots = kLsSlots;               // per-loader ring of index octets (16 words a slot)
     constexpr int kGroup = GATHER ? 9 : 8;         // vector-memory operations of a loader's group (without the mask bits)
-    typedef __attribute__((address_space(3))) char* lds_wp;
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_wp)lds;
+    const unsigned lds_base = lds_addr(lds);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int32_t colsum_all = colsum_arg & 0xff, colsum_of = colsum_for(colsum_arg, ch.rel);   // (a chunk of another relation: zeros)
@@ -881,7 +857,7 @@ __device__ __forceinline__ void wgrad_ls_body(const bf16_t* __restrict__ A, cons
         const int q = wave - kLsCompute;
         const int rin = lane / LPRW, cpos = lane % LPRW;
         const char* zero = reinterpret_cast<const char*>(g_zero_row);
-        const unsigned idx_base = (unsigned)(uintptr_t)(lds_wp)&idxL[GATHER ? q : 0][0][0];
+        const unsigned idx_base = lds_addr(&idxL[GATHER ? q : 0][0][0]);
         int gch[4];                                // source byte offset inside the row, per piece (the XOR swizzle of the image)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -1393,8 +1369,7 @@ __global__ __launch_bounds__(kTfThreads, (D == 1 ? 4 : 2)) void rows_transform_k
                 const int col = n0 + n * 16 + 4 * (lane >> 4);
                 float v[4] = {acc[m][n][0], acc[m][n][1], acc[m][n][2], acc[m][n][3]};
                 if (bias) {
-                    typedef bf16_t bf16x4b __attribute__((ext_vector_type(4)));
-                    const bf16x4b bv = *reinterpret_cast<const bf16x4b*>(biasL + col);   // written by this wave: in order
+                    const bf16x4 bv = *reinterpret_cast<const bf16x4*>(biasL + col);   // written by this wave: in order
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] += (float)bv[i];
                 }
@@ -1402,7 +1377,6 @@ __global__ __launch_bounds__(kTfThreads, (D == 1 ? 4 : 2)) void rows_transform_k
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] = dn_act(v[i], slope);
                 }
-                typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
                 bf16x4 o;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = (bf16_t)v[i];
@@ -1422,12 +1396,10 @@ __global__ __launch_bounds__(kTfThreads, (D == 1 ? 4 : 2)) void rows_transform_k
                 if (mask_pos)                                    // activation backward: keep where the saved activation is > 0
                     v = dn_keep_or_scale_mask(v, *reinterpret_cast<const uint4*>(mask_pos + (size_t)p * HO + c * 8), slope);
                 if (sc1_store) {
-                    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
                     const u32x4 vv = {v.x, v.y, v.z, v.w};
                     asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(Y + (size_t)p * HO + c * 8), "v"(vv) : "memory");
                 }
                 else if (nt_store) {
-                    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
                     const u32x4 vv = {v.x, v.y, v.z, v.w};
                     __builtin_nontemporal_store(vv, reinterpret_cast<u32x4*>(Y + (size_t)p * HO + c * 8));
                 }
@@ -1475,7 +1447,6 @@ __global__ __launch_bounds__(H * 4) void rows_selfsum_kernel(const bf16_t* __res
                                                              const int32_t* __restrict__ lrows, int32_t P_edge, int32_t drop_beg,
                                                              int32_t drop_end) {
     constexpr int T = H * 4, K = kSsSlots;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     constexpr int SX = H + kPad, SY = H + kPad;
     constexpr int KS = H / 32, MT = kSsRows / 16;
     constexpr int LPR = H / 8;                                   // 16-byte pieces per row
@@ -1577,7 +1548,6 @@ __global__ __launch_bounds__(H * 4) void rows_selfsum_kernel(const bf16_t* __res
         // the tile is staged in fp32 halves?  no: bf16, like the rows it is added to (both are rounded once)
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-            typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
             bf16x4 o;
 #pragma unroll
             for (int i = 0; i < 4; ++i) o[i] = (bf16_t)acc[m][i];
@@ -1709,8 +1679,6 @@ __global__ __launch_bounds__(H * 4) void rows_chain2_kernel(const bf16_t* __rest
     // the two products overlap and every wave re-reads the 32-row LDS tile for 32 columns instead of 16 (LDS fragment reads
     // were the limiter of the one-role-per-wave version: 16 waves x 16 KB per stage).
     constexpr int T = H * 4;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
     constexpr int SX = H + kPad;
     constexpr int KS = H / 32, MT = kSsRows / 16, NT = 2;
     constexpr int LPR = H / 8;                                   // 16-byte pieces = mask bytes per row
@@ -1744,7 +1712,7 @@ __global__ __launch_bounds__(H * 4) void rows_chain2_kernel(const bf16_t* __rest
     bf16x8 wf[KS][NT];
     if (flags & (role ? 16 : 8)) {                               // this layer's weights are stored [k][n] (a Linear's own weight seen
         // from the input-gradient side): transposed through a wave-private scratch in buf1 / buf2 (idle until the first barrier)
-        dn_load_w_kn32p<KS>(Wn, H, n0, lane, reinterpret_cast<char*>(buf1(0)) + wave * 2048, wf);
+        dn_load_w_kn32<KS, true>(Wn, H, n0, lane, reinterpret_cast<char*>(buf1(0)) + wave * 2048, wf);
     } else {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)

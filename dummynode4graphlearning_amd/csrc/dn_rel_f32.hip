@@ -20,13 +20,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16_t;
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
-typedef short short4v __attribute__((ext_vector_type(4)));
-typedef short short8v __attribute__((ext_vector_type(8)));
-
 // x = hi + lo (+ O(2^-17 |x|)): hi = bf16(x) (round to nearest even), lo = bf16(x - hi)
 __device__ __forceinline__ void split4(const float4& v, bf16x4& hi, bf16x4& lo) {
     const float f[4] = {v.x, v.y, v.z, v.w};
@@ -44,17 +37,6 @@ __device__ __forceinline__ void split8(const float4& a, const float4& b, bf16x8&
         lo[i] = (bf16_t)(f[i] - (float)hi[i]);
     }
 }
-// fragment of a K-strided bf16 operand held row-major in LDS (hardware transpose read, as dn_rel.hip:tr_frag)
-__device__ __forceinline__ bf16x8 tr_frag16(const bf16_t* tile, int stride, int col0, int lane) {
-    const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-    const bf16_t* a0 = tile + (8 * g + q) * stride + col0 + 4 * p;
-    typedef short4v __attribute__((address_space(3))) * lds_p;
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0));
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0 + 4 * stride));
-    const short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, f);
-}
-
 constexpr int kThreads = 512;
 constexpr int kRows = 32;
 
@@ -72,10 +54,6 @@ struct WeightForm {
         if (bias_rel < 0) return bias + (size_t)rel * H;
         return rel == bias_rel ? bias : nullptr;
     }
-};
-
-struct Chunk {
-    int32_t rel, beg, end, pad;
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -310,13 +288,13 @@ __device__ __forceinline__ void rows_wgrad_f32s_body(const float* __restrict__ A
         bf16x8 gh[NT], gl[NT];
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-            gh[n] = tr_frag16(tile(b, 2), S, n0 + n * 16, lane);
-            gl[n] = tr_frag16(tile(b, 3), S, n0 + n * 16, lane);
+            gh[n] = tr_frag(tile(b, 2), S, n0 + n * 16, lane);
+            gl[n] = tr_frag(tile(b, 3), S, n0 + n * 16, lane);
         }
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-            const bf16x8 ah = tr_frag16(tile(b, 0), S, k0 + m * 16, lane);
-            const bf16x8 al = tr_frag16(tile(b, 1), S, k0 + m * 16, lane);
+            const bf16x8 ah = tr_frag(tile(b, 0), S, k0 + m * 16, lane);
+            const bf16x8 al = tr_frag(tile(b, 1), S, k0 + m * 16, lane);
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
                 acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, gh[n], acc[m][n], 0, 0, 0);

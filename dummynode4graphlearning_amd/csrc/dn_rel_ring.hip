@@ -42,15 +42,6 @@
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-struct Tile {
-    int32_t rel, beg, end, pad;
-};
-
 constexpr int kH = 256;
 constexpr int kRowB = 2 * kH;          // bytes per row
 constexpr int kTR = 32;                // rows per tile
@@ -62,14 +53,6 @@ constexpr int kRowsPerLoader = kTR / kLoaders;      // 8
 constexpr int kDmaPerTile = kRowsPerLoader / 2;     // 4 DMA wave-instructions per loader and tile (2 rows each)
 constexpr int kBatch = 8;                           // tiles per batch of records / indices
 constexpr int kRecRing = 32, kIdxRing = 16, kDescRing = 32;
-
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-    typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (bf16_t)a;
-    v[1] = (bf16_t)b;
-    return __builtin_bit_cast(uint32_t, v);
-}
 
 #ifdef DN_RING_STATS
 // diagnostic build (-DDN_RING_STATS): cycle counters of the last launch, per workgroup: compute wave 0 {loop, barrier wait, reads + MFMAs, epilogue},
@@ -84,8 +67,6 @@ __device__ unsigned long long g_ring_stats[256][10];
 
 __device__ int32_t g_zero_idx[64];     // row 0 (device globals are zero-initialised): what an EMPTY tile's rows gather
 
-#define DN_DS_READ128(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
-
 // SEG (the dense form only: rows in order, one source, no epilogue): a tile's record carries s0 | s1 << 8 in its fourth word and the
 // launch also writes, per tile, the sum of its rows beg + s0 .. beg + s1 - 1 to seg_out [num_tiles, 256] -- taken by the LOADERS (one
 // column a lane, 4 x 64 = 256) from the landed stage, row by row in fp32 from zero and rounded once: dn_gather_segsum_bf16's order
@@ -95,16 +76,15 @@ template <bool MASK, bool IDX, bool EPI, bool HASX2, bool SEG = false>
 __global__ __launch_bounds__(kThreads) void rows_transform_ring_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ X2, int32_t n1, const int32_t* __restrict__ idx,
     const bf16_t* __restrict__ Wn, const bf16_t* __restrict__ bias, int32_t flags, const bf16_t* __restrict__ mask_pos,
-    const Tile* __restrict__ tiles, int32_t num_tiles, int32_t tiles_per_wg, bf16_t* __restrict__ Y, float slope,
+    const Chunk* __restrict__ tiles, int32_t num_tiles, int32_t tiles_per_wg, bf16_t* __restrict__ Y, float slope,
     bf16_t* __restrict__ seg_out) {
     __shared__ __attribute__((aligned(1024))) char lds[kNS * kStageB];
     __shared__ __attribute__((aligned(16))) int32_t descL[kDescRing][4]; // tile records for the compute waves (copied by loader 0)
     __shared__ __attribute__((aligned(128))) int32_t recR[kLoaders][kRecRing][4];            // loader-private rings: tile records
     __shared__ __attribute__((aligned(256))) int32_t idxR[kLoaders][kIdxRing][kRowsPerLoader];  // ... and row indices, by LDS-DMA
     __shared__ __attribute__((aligned(16))) char wscr[kCompute][2048];     // per compute wave: transposition scratch of [k][n] weights
-    typedef __attribute__((address_space(3))) char* lds_wp;
-    const unsigned lds_base = (unsigned)(uintptr_t)(lds_wp)lds;
-    const unsigned desc_base = (unsigned)(uintptr_t)(lds_wp)&descL[0][0];
+    const unsigned lds_base = lds_addr(lds);
+    const unsigned desc_base = lds_addr(&descL[0][0]);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t_beg = (int)blockIdx.x * tiles_per_wg;
@@ -124,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void rows_transform_ring_kernel(
         for (int c = 0; c < 8; ++c) {
             const int k = 64 * c + lane;
             live[c] = false;
-            if (k < nt) { const Tile tl = tiles[k]; live[c] = tl.end > tl.beg; }
+            if (k < nt) { const Chunk tl = tiles[k]; live[c] = tl.end > tl.beg; }
         }
         int last = -1;
 #pragma unroll
@@ -154,8 +134,8 @@ __global__ __launch_bounds__(kThreads) void rows_transform_ring_kernel(
             const int rl = kRowsPerLoader * q + 2 * j + rin;               // row of the stage this lane fills
             swoff[j] = (pos ^ (rl & 15)) * 16;                             // source byte offset inside the row
         }
-        const unsigned rec_base = (unsigned)(uintptr_t)(lds_wp)&recR[q][0][0];
-        const unsigned idx_base = (unsigned)(uintptr_t)(lds_wp)&idxR[q][0][0];
+        const unsigned rec_base = lds_addr(&recR[q][0][0]);
+        const unsigned idx_base = lds_addr(&idxR[q][0][0]);
         // the index ring holds a tile's 8 rows as {0, 2, 4, 6, 1, 3, 5, 7}: the four rows a lane needs (2 j + rin) are one 16-byte read
         const int myrow = 2 * (lane & 3) + ((lane >> 2) & 1);              // row (of my 8) whose index lane 8 k + l fetches
         auto dma_recs = [&](int T0) {                                      // records of tiles T0 .. T0 + 7 (clamped: valid memory)
@@ -186,7 +166,6 @@ __global__ __launch_bounds__(kThreads) void rows_transform_ring_kernel(
         const char* srcA[kDmaPerTile];
         const char* srcB[kDmaPerTile];
         auto prep = [&](int u, const char* (&src)[kDmaPerTile]) {
-            typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
             const i32x4 iv = *reinterpret_cast<const i32x4*>(&idxR[q][u % kIdxRing][4 * rin]);   // rows rin, 2 + rin, 4 + rin, 6 + rin
 #pragma unroll
             for (int j = 0; j < kDmaPerTile; ++j) {
@@ -503,7 +482,6 @@ __global__ __launch_bounds__(kThreads) void rows_transform_ring_kernel(
     }
 #endif
 }
-#undef DN_DS_READ128
 
 }  // namespace
 
@@ -524,7 +502,7 @@ int launch_transform_ring256(const void* X_, const void* X2, int32_t n1, const i
 #define DN_RING_LAUNCH(M, I, E, X)                                                                                      \
     hipLaunchKernelGGL((rows_transform_ring_kernel<M, I, E, X>), dim3((unsigned)grid), dim3(kThreads), 0, st, (const bf16_t*)X_, \
                        (const bf16_t*)X2, n1, idx, (const bf16_t*)Wn, (const bf16_t*)bias, flags, (const bf16_t*)mask_pos,      \
-                       reinterpret_cast<const Tile*>(tiles), (int32_t)num_tiles, (int32_t)tiles_per_wg, (bf16_t*)Y, slope,      \
+                       reinterpret_cast<const Chunk*>(tiles), (int32_t)num_tiles, (int32_t)tiles_per_wg, (bf16_t*)Y, slope,      \
                        (bf16_t*)nullptr)
     // the conv's launches (gathered rows, no epilogue, one source) get the leanest instruction stream: the loop is bound by
     // vector-instruction issue, not by the matrix pipe (~180 VALU instructions per SIMD and tile before this split)
@@ -553,7 +531,7 @@ int launch_transform_ring256_seg(const void* X, const void* W_kn, const int32_t*
     const int32_t flags = 2 | 4;                                           // streaming stores, W as the parameter stores it ([k][n])
     hipLaunchKernelGGL((rows_transform_ring_kernel<false, false, false, false, true>), dim3((unsigned)grid), dim3(kThreads), 0, st,
                        (const bf16_t*)X, (const bf16_t*)nullptr, 0x7fffffff, (const int32_t*)nullptr, (const bf16_t*)W_kn,
-                       (const bf16_t*)nullptr, flags, (const bf16_t*)nullptr, reinterpret_cast<const Tile*>(tiles), (int32_t)num_tiles,
+                       (const bf16_t*)nullptr, flags, (const bf16_t*)nullptr, reinterpret_cast<const Chunk*>(tiles), (int32_t)num_tiles,
                        (int32_t)tiles_per_wg, (bf16_t*)Y, 0.f, (bf16_t*)seg_sums);
     DN_CHECK_LAUNCH();
     return DN_OK;

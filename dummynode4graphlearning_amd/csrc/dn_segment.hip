@@ -18,8 +18,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kSegsPerGroup = 2;  // segments a row group walks per block (chunk = groups * this)
 
-typedef __bf16 bf16_t;
-
 template <typename T> struct Vec;
 template <> struct Vec<float> {
     static constexpr int N = 4;
@@ -43,7 +41,6 @@ template <> struct Vec<bf16_t> {
         }
     }
     static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) {
-        typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
         bf16x8 o;
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = (bf16_t)v[i];  // v_cvt_pk_bf16_f32: RNE, NaN stays NaN

@@ -15,12 +15,6 @@ constexpr int kWgradMaxH = 256;                   // (its LDS stage: kWgradChunk
 constexpr int kWgradMaxK = 64;
 constexpr int kEmbedMaxLds = 16384;               // fp32 words of the two staged embedding weights (64 KB)
 
-typedef __bf16 bf16_t;
-
-__device__ __forceinline__ float ld(const float* p, int64_t i) { return p[i]; }
-__device__ __forceinline__ float ld(const bf16_t* p, int64_t i) { return (float)p[i]; }
-template <typename T> __device__ __forceinline__ T st(float x) { return (T)x; }
-
 // meta = {Lp, Lg, flags, 0}: Lp / Lg = longest pattern / graph of the batch.  Every block reduces the pattern lengths itself
 // (B int loads, L2-resident) so that the label-0 rule below needs no second launch.
 template <typename T>

@@ -18,11 +18,22 @@ I32 = torch.int32
 
 class KernelTimer:
     """Optional HIP-event timing of individual kernel launches on the current stream (bench.py's roofline leg).
-    Events are recorded on the stream the kernel is launched on; elapsed times are read after a synchronize."""
+    Events are recorded on the stream the kernel is launched on; elapsed times are read after a synchronize.
+    `with KernelTimer() as t:` times the launches of the block: it installs t as ops.kernel_timer and puts back what it found."""
 
     def __init__(self):
         self.records = []  # (tag, start_event, end_event)
         self.enabled = True
+
+    def __enter__(self):
+        global kernel_timer
+        self.found, kernel_timer = kernel_timer, self
+        return self
+
+    def __exit__(self, *exc):
+        global kernel_timer
+        kernel_timer = self.found
+        return False
 
     def launch(self, tag, fn):
         if not self.enabled:
@@ -225,36 +236,54 @@ WGRAD_CHUNK_ROWS = int(_os.environ.get("DN_WGRAD_CHUNK", "4096"))            # s
 # the launch is ONE round of workgroups, up to this many rows (config 5: 775 chunks of 4,096 rows = 3.03 rounds of 256 workgroups and
 # 203 MB of partial products became 245 chunks of 12,864 rows and 64 MB: conv weight gradient + reduce 534 -> 473 us, round 6)
 WGRAD_CHUNK_CAP = max(WGRAD_CHUNK_ROWS, int(_os.environ.get("DN_WGRAD_CHUNK_CAP", "65536")))
+
+
+class _ThreadSwitch:
+    """The base of every path switch below (f32_exact, dual_fused, ..., attn_fused): a context manager that sets the calling THREAD's
+    override in its class's slot to `on`, keeps the value it found and puts it back on exit, also when the body raises.  No override
+    (None): the module default holds, read by the *_enabled() function of the switch when it is called.  A subclass with
+    _inverse = True writes the opposite value into the slot it inherits (dual_composed / lrp_composed)."""
+    _tls = _threading.local()            # one entry per slot in the thread's own dict (reading it there, a miss costs no AttributeError:
+    _slot = None                         # f32_mode() runs in every autograd forward)
+    _inverse = False
+
+    def __init__(self, on=True):
+        self.on = bool(on) != self._inverse
+
+    def __enter__(self):
+        mine = self._tls.__dict__
+        self.old = mine.get(self._slot)
+        mine[self._slot] = self.on
+        return self
+
+    def __exit__(self, *exc):
+        self._tls.__dict__[self._slot] = self.old
+        return False
+
+    @classmethod
+    def override(cls, default=None):
+        """The calling thread's override of this switch, `default` when there is none."""
+        m = cls._tls.__dict__.get(cls._slot)
+        return default if m is None else m
+
+
 # fp32 matrix products: False = 3-term bf16 split on the fast MFMA path (1e-5-level agreement with exact f32, inside the
 # reference's 1e-4 bar), True = exact f32 MFMA (1/16 of the bf16 rate; the checker).  F32_EXACT is the PROCESS default (read once
 # from the environment; assignable); `with f32_exact(...)` overrides it for the calling THREAD only, and every autograd function
 # below records the mode its forward ran in and runs its backward in the same mode -- whatever thread autograd uses for it and
 # whether or not the `with` block has been left by then.
 F32_EXACT = _os.environ.get("DN_F32_EXACT", "0") == "1"
-_f32_tls = _threading.local()
+
+
+class f32_exact(_ThreadSwitch):
+    """Context manager: run the fp32 matrix kernels inside it on the exact-f32 MFMA (True) or on the bf16 split (False).
+    Thread-local; backward passes of work recorded inside it keep the mode (see F32_EXACT)."""
+    _slot = "f32_exact"
 
 
 def f32_mode():
     """The fp32 arithmetic a kernel launched NOW from this thread uses: the thread's f32_exact override, else ops.F32_EXACT."""
-    m = getattr(_f32_tls, "mode", None)
-    return F32_EXACT if m is None else m
-
-
-class f32_exact:
-    """Context manager: run the fp32 matrix kernels inside it on the exact-f32 MFMA (True) or on the bf16 split (False).
-    Thread-local; backward passes of work recorded inside it keep the mode (see F32_EXACT)."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_f32_tls, "mode", None)
-        _f32_tls.mode = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _f32_tls.mode = self.old
-        return False
+    return f32_exact.override(F32_EXACT)
 
 
 def _backward_in_forward_mode(backward):
@@ -3259,7 +3288,6 @@ def si_read_meta_pair(meta_v, meta_e, need_edges=True):
 # ----------------------------------------------------------------------------------------------
 DUAL_EDGE, DUAL_SUB, DUAL_MULT = 0, 1, 2
 DUAL_MAX_H = 256
-_dual_tls = _threading.local()
 
 
 # The layers' default.  Measured on the scale batch (docs/LAB_NOTES.md "SI count models: CompGCN / DMPNN"): the fused DMPLayer and
@@ -3271,33 +3299,19 @@ DUAL_FUSED_DEFAULT = False
 def dual_fused_enabled():
     """Do CompGCNLayer / DMPLayer forwards started NOW on this thread take dn_dual.hip?  The thread's dual_fused / dual_composed
     override, else ops.DUAL_FUSED_DEFAULT."""
-    m = getattr(_dual_tls, "fused", None)
-    return DUAL_FUSED_DEFAULT if m is None else m
+    return dual_fused.override(DUAL_FUSED_DEFAULT)
 
 
-class dual_fused:
+class dual_fused(_ThreadSwitch):
     """Context manager: CompGCNLayer (sub, mult) / DMPLayer forwards started inside it (on this thread) run on the fused dual
     kernels (dn_dual.hip) where the predicate of dual.py allows it.  Their backward passes use the same kernels whenever they run."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_dual_tls, "fused", None)
-        _dual_tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _dual_tls.fused = self.old
-        return False
+    _slot = "dual_fused"
 
 
 class dual_composed(dual_fused):
     """Context manager: force the composed path (generic segment kernels + torch glue) for the layers inside it, whatever the
     default -- for tests and A/B runs.  dual_composed(False) = dual_fused()."""
-
-    def __init__(self, on=True):
-        super().__init__(not on)
+    _inverse = True
 
 
 def dual_supported(*tensors):
@@ -3569,7 +3583,6 @@ LRP_PAIR_NODES = 64
 # path is the default and the fused kernels are an opt-in (`with ops.lrp_fused():`) -- and the path of a batch whose sequence
 # list does not fit the materialised index (hub egos), where the composed path cannot run at all.
 LRP_FUSED_DEFAULT = False
-_lrp_tls = _threading.local()
 _INT32_MAX = 2 ** 31 - 1
 
 
@@ -3579,32 +3592,18 @@ def lrp_stage_nodes(H, seq_len):
 
 
 def lrp_fused_enabled():
-    m = getattr(_lrp_tls, "fused", None)
-    return LRP_FUSED_DEFAULT if m is None else m
+    return lrp_fused.override(LRP_FUSED_DEFAULT)
 
 
-class lrp_fused:
+class lrp_fused(_ThreadSwitch):
     """Context manager: ops.lrp_pool calls started inside it (on this thread) run on dn_lrp_pool_* where the width allows it."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_lrp_tls, "fused", None)
-        _lrp_tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _lrp_tls.fused = self.old
-        return False
+    _slot = "lrp_fused"
 
 
 class lrp_composed(lrp_fused):
     """Context manager: force the composed path (gather_segsum over the materialised index + dn_segment_mean / _sum), whatever
     the default -- the A/B partner of the fused kernels and the path of widths they do not take."""
-
-    def __init__(self, on=True):
-        super().__init__(not on)
+    _inverse = True
 
 
 # The default path of ops.lrp_pool_linear (the pooling of a DMPLRP layer): the collapsed index (LrpIndex.collapsed) or
@@ -3615,25 +3614,13 @@ LRP_COLLAPSED_DEFAULT = True
 
 
 def lrp_collapsed_enabled():
-    m = getattr(_lrp_tls, "collapsed", None)
-    return LRP_COLLAPSED_DEFAULT if m is None else m
+    return lrp_collapsed.override(LRP_COLLAPSED_DEFAULT)
 
 
-class lrp_collapsed:
+class lrp_collapsed(_ThreadSwitch):
     """Context manager: ops.lrp_pool_linear calls started inside it (on this thread) pool over the collapsed index (on=True) or
     through ops.lrp_pool(act="none", factor=None) (on=False: the composed or fused path, as ops.lrp_fused / lrp_composed say)."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_lrp_tls, "collapsed", None)
-        _lrp_tls.collapsed = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _lrp_tls.collapsed = self.old
-        return False
+    _slot = "lrp_collapsed"
 
 
 def lrp_fused_supported(H):
@@ -3913,7 +3900,7 @@ def lrp_pool(x, edge_feat, weight, bias, factor, graph, seq_len=4, act="relu", p
     if x.shape[0] != ix.num_nodes or edge_feat.shape[0] != ix.num_edges:
         raise _lib.DnHipError("lrp_pool: one x row per node and one edge_feat row per edge of the indexed batch expected")
     t_node, t_edge, H = _lrp_tables(x, edge_feat, weight, L)
-    forced = getattr(_lrp_tls, "fused", None)
+    forced = lrp_fused.override()
     fused = (LRP_FUSED_DEFAULT or not ix.materialisable()) if forced is None else forced
     if fused and lrp_fused_supported(H) and x.dtype == torch.float32:
         slope = LRP_LEAKY_SLOPE if act == "leaky_relu" else 0.0
@@ -3974,7 +3961,6 @@ def lrp_pool_linear(x, edge_feat, weight, bias, graph, seq_len=4, pool="mean"):
 # ----------------------------------------------------------------------------------------------
 HGT_MAX_H = 256
 HGT_HEADS = (1, 2, 4, 8)
-_hgt_tls = _threading.local()
 
 # The layers' default.  Measured on the scale batch (docs/LAB_NOTES.md "SI count models: HGT"; H = 64, 4 heads, 14 relations, 25.6 k
 # nodes, 155 k edges, fused and composed alternated in one process): the layer step 1.72 against 2.54 ms, the model step 10.4 against
@@ -3984,25 +3970,13 @@ HGT_FUSED_DEFAULT = True
 
 
 def hgt_fused_enabled():
-    m = getattr(_hgt_tls, "fused", None)
-    return HGT_FUSED_DEFAULT if m is None else m
+    return hgt_fused.override(HGT_FUSED_DEFAULT)
 
 
-class hgt_fused:
+class hgt_fused(_ThreadSwitch):
     """Context manager: HeteroGraphTransLayer forwards started inside it (on this thread) run their attention on dn_hgt.hip (on=True)
     where hgt_fused_supported allows it, or on the composed path (on=False: torch scatter ops over the same factorisation)."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_hgt_tls, "fused", None)
-        _hgt_tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _hgt_tls.fused = self.old
-        return False
+    _slot = "hgt_fused"
 
 
 def hgt_fused_supported(x, heads):
@@ -4285,29 +4259,8 @@ def hgt_message_pass(q, k, v, att, msg, pri, ix, scale):
     return hgt_pair_reduce(U, w_msg, ix)
 
 
-# ------------------------------------------------------------------------------------------------ graph-kernel switches
-class _GraphKernelSwitch:
-    """The base of wl_fused / gk_fused / kwl_fused / k3wl_fused: a context manager that sets its subclass's thread-local slot `_tls.fused`
-    to `on`, keeps the value it found and puts it back on exit (None: no override, the *_FUSED_DEFAULT holds)."""
-    _tls = None
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(self._tls, "fused", None)
-        self._tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        self._tls.fused = self.old
-        return False
-
-
 # ------------------------------------------------------------------------------------------------ WL / WLOA graph kernels
 # (dn_wl.hip; the dataset side -- reader, node classes, features, command line -- is graph_kernels.py)
-_wl_tls = _threading.local()
-
 # The default of graph_kernels.wl_colors.  Measured by tools/graph_kernel_bench.py (docs/LAB_NOTES.md "Graph kernels: WL / WLOA"; 4096
 # NCI1-shaped graphs with dummy nodes, H = 5, fused and composed alternated in one process): 0.13 against 1.99 ms for the five
 # refinement steps, 0.27 against 2.95 ms with edge labels, spreads below 4 % -- far outside the spread, so the fused kernels are the default.
@@ -4315,15 +4268,14 @@ WL_FUSED_DEFAULT = True
 
 
 def wl_fused_enabled():
-    m = getattr(_wl_tls, "fused", None)
-    return WL_FUSED_DEFAULT if m is None else m
+    return wl_fused.override(WL_FUSED_DEFAULT)
 
 
-class wl_fused(_GraphKernelSwitch):
+class wl_fused(_ThreadSwitch):
     """Context manager: WL colour refinements started inside it (on this thread) sort in registers and LDS (on=True: dn_wl_refine_u64,
     lists of up to wl_max_entries() entries; longer ones take the composed path either way) or on the composed path (on=False: a
     device-wide segmented sort with torch ops, then dn_wl_fold_u64)."""
-    _tls = _wl_tls
+    _slot = "wl_fused"
 
 
 def wl_max_entries():
@@ -4387,8 +4339,6 @@ def wl_gram(feat_ptr, feat_color, feat_count, feat_step, num_graphs, num_steps, 
 
 # ------------------------------------------------------------------------------------------------ SP / GR graph kernels
 # (dn_gk.hip; the dataset side -- graph and centre classes, label ranks, composed paths, command line -- is graph_kernels_spgr.py)
-_gk_tls = _threading.local()
-
 # The defaults of graph_kernels_spgr.sp_features / gr_features, one per kernel.  Measured by tools/graph_kernel_spgr_bench.py
 # (docs/LAB_NOTES.md "Graph kernels: SP / GR"), fused and composed alternated in one process: 4096 NCI1-shaped graphs with dummy nodes,
 # SP 1.54 against 5.24 ms and GR 1.51 against 3.75 ms; 300 DD-shaped graphs, SP 105.1 against 110.7 ms and GR 103.1 against 161.7 ms;
@@ -4398,16 +4348,16 @@ GK_FUSED_DEFAULT = {"SP": True, "GR": True}
 
 def gk_fused_enabled(kernel=None):
     """Whether `kernel` ("SP" or "GR") takes the dn_gk_* kernels; without a kernel: whether both do."""
-    m = getattr(_gk_tls, "fused", None)
+    m = gk_fused.override()
     if m is not None:
         return m
     return all(GK_FUSED_DEFAULT.values()) if kernel is None else GK_FUSED_DEFAULT[kernel]
 
 
-class gk_fused(_GraphKernelSwitch):
+class gk_fused(_ThreadSwitch):
     """Context manager: SP / GR feature builds started inside it (on this thread) run the dn_gk_* kernels (on=True; SP graphs above
     gk_sp_lds_max_nodes() nodes take the composed path either way) or the composed torch-op path (on=False)."""
-    _tls = _gk_tls
+    _slot = "gk_fused"
 
 
 def gk_sp_lds_max_nodes():
@@ -4435,8 +4385,6 @@ def gk_gr_keys(num_nodes, group, item_node, item_row0, item_row1, item_offset, c
 
 # ------------------------------------------------------------------------------------------------ 2-WL graph kernels
 # (dn_kwl.hip; the dataset side -- tuples, classes, composed path, features, command line -- is graph_kernels_kwl.py)
-_kwl_tls = _threading.local()
-
 # The default of graph_kernels_kwl.kwl_colors.  Measured by tools/graph_kernel_kwl_bench.py (docs/LAB_NOTES.md "Graph kernels: 2-WL"),
 # fused and composed alternated in one process, initial colours + 3 steps: 512 NCI1-shaped graphs with dummy nodes, WL 0.93 against
 # 94.5 ms, DWL 2.29 / 99.0, LWL 0.44 / 11.9, LWLC 0.23 / 5.7; 128 PROTEINS-shaped graphs (one above 128 nodes, composed either way), WL
@@ -4446,15 +4394,14 @@ KWL_FUSED_DEFAULT = True
 
 
 def kwl_fused_enabled():
-    m = getattr(_kwl_tls, "fused", None)
-    return KWL_FUSED_DEFAULT if m is None else m
+    return kwl_fused.override(KWL_FUSED_DEFAULT)
 
 
-class kwl_fused(_GraphKernelSwitch):
+class kwl_fused(_ThreadSwitch):
     """Context manager: 2-WL refinements started inside it (on this thread) run the dn_kwl_* kernels (on=True; graphs above
     kwl_max_nodes() nodes (WL / DWL) or with a degree above kwl_max_entries() (LWL / LWLC) take the composed path either way) or the
     composed path (on=False: torch device ops, a device-wide segmented sort and dn_wl_fold_u64)."""
-    _tls = _kwl_tls
+    _slot = "kwl_fused"
 
 
 def kwl_max_nodes():
@@ -4519,8 +4466,6 @@ def kwl_fold_from_max(seg, key, num_segments):
 
 # ------------------------------------------------------------------------------------------------ 3-WL graph kernels
 # (dn_k3wl.hip; the dataset side -- items, classes, composed path, features, command line -- is graph_kernels_k3wl.py)
-_k3wl_tls = _threading.local()
-
 # The default of graph_kernels_k3wl.k3wl_colors, one per kernel.  Measured by tools/graph_kernel_k3wl_bench.py (docs/LAB_NOTES.md
 # "Graph kernels: 3-WL"), fused and composed alternated in one process, initial colours + 2 steps: 188 MUTAG-shaped graphs with dummy
 # nodes, WL 0.84 against 222.7 ms, DWL 0.85 / 234.4, LWL 1.60 / 40.8, LWLC 1.05 / 12.1; 16 graphs of about 40 nodes, WL 0.94 / 230.8,
@@ -4531,17 +4476,17 @@ K3WL_FUSED_DEFAULT = {"WL": True, "DWL": True, "LWL": True, "LWLC": True}
 
 def k3wl_fused_enabled(kernel=None):
     """Whether `kernel` ("WL", "DWL", "LWL" or "LWLC") takes the dn_k3wl_* kernels; without a kernel: whether all four do."""
-    m = getattr(_k3wl_tls, "fused", None)
+    m = k3wl_fused.override()
     if m is not None:
         return m
     return all(K3WL_FUSED_DEFAULT.values()) if kernel is None else K3WL_FUSED_DEFAULT[kernel]
 
 
-class k3wl_fused(_GraphKernelSwitch):
+class k3wl_fused(_ThreadSwitch):
     """Context manager: 3-WL refinements started inside it (on this thread) run the dn_k3wl_* kernels (on=True; graphs above
     k3wl_max_nodes() nodes (WL / DWL) or with a degree above k3wl_max_entries() (LWL / LWLC) take the composed path either way) or the
     composed path (on=False: torch device ops, a device-wide segmented sort and dn_wl_fold_u64)."""
-    _tls = _k3wl_tls
+    _slot = "k3wl_fused"
 
 
 def k3wl_max_nodes():
@@ -4597,7 +4542,6 @@ SEG_ATTN_MAX_KEYS = 1024           # dn_seg_attn_max_keys(): above, the composed
 SEG_POOL_MAX_MEM = 64
 SEG_SCORES = {"sparsemax": 0, "softmax": 1}
 SEG_POOL_MODES = {"mean": 0, "sum": 1, "max": 2}
-_attn_tls = _threading.local()
 
 # The heads' default.  Measured on the scale batch (docs/LAB_NOTES.md "SI count heads: attention / DIAMNet"; 512 pairs, hidden 64, 4
 # heads, fused and composed alternated in one process): the MeanAttnPredictNet head 2.99 against 6.01 ms on the node rows and 15.6
@@ -4608,25 +4552,13 @@ ATTN_FUSED_DEFAULT = True
 
 
 def attn_fused_enabled():
-    m = getattr(_attn_tls, "fused", None)
-    return ATTN_FUSED_DEFAULT if m is None else m
+    return attn_fused.override(ATTN_FUSED_DEFAULT)
 
 
-class attn_fused:
+class attn_fused(_ThreadSwitch):
     """Context manager: seg_attention / seg_window_pool calls made inside it (on this thread) run on dn_seg_attn.hip (on=True) where
     attn_fused_supported allows it, or on the composed path (on=False: the padded torch computation of attn_pred.py on the ragged rows)."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_attn_tls, "fused", None)
-        _attn_tls.fused = self.on
-        return self
-
-    def __exit__(self, *exc):
-        _attn_tls.fused = self.old
-        return False
+    _slot = "attn_fused"
 
 
 def attn_fused_supported(x, heads, max_k=1):

@@ -140,13 +140,9 @@ def test_rgin_layer_at_the_default_width_takes_one_launch_per_direction():
             for p in layer.parameters():
                 p.grad = None
             x = x0.clone().requires_grad_(True)
-            timer = ops.KernelTimer()
-            ops.kernel_timer = timer
-            try:
+            with ops.KernelTimer() as timer:
                 out, _ = layer(g, x, et)
                 out.backward(coef)
-            finally:
-                ops.kernel_timer = None
             return [r[0] for r in timer.records], [out.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in layer.parameters()]
         finally:
             ops.CONV_GRAPHS_ENABLED = old
@@ -214,13 +210,9 @@ def test_fp32_rgin_layer_takes_one_weight_gradient_launch(H, act):
         for p in layer.parameters():
             p.grad = None
         x = x0.clone().requires_grad_(True)
-        timer = ops.KernelTimer()
-        ops.kernel_timer = timer
-        try:
+        with ops.KernelTimer() as timer:
             out, _ = layer(g, x, et)
             out.backward(coef)
-        finally:
-            ops.kernel_timer = None
         return [r[0] for r in timer.records], [out.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in layer.parameters()]
 
     tags, got = run()
@@ -281,13 +273,9 @@ def test_fp32_rep_net_carries_the_residual_in_the_layer_launches():
         for p in net.parameters():
             p.grad = None
         x = x0.clone().requires_grad_(True)
-        timer = ops.KernelTimer()
-        ops.kernel_timer = timer
-        try:
+        with ops.KernelTimer() as timer:
             out = net.get_graph_rep(g, x)
             out.backward(coef)
-        finally:
-            ops.kernel_timer = None
         return [r[0] for r in timer.records], [out.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in net.parameters()]
 
     tags, got = run()
@@ -348,13 +336,9 @@ def test_wide_rgin_layer_takes_one_weight_gradient_launch(act, graphs):
         for p in layer.parameters():
             p.grad = None
         x = x0.clone().requires_grad_(True)
-        timer = ops.KernelTimer()
-        ops.kernel_timer = timer
-        try:
+        with ops.KernelTimer() as timer:
             out, _ = layer(g, x, et)
             out.backward(coef)
-        finally:
-            ops.kernel_timer = None
         return ([r[0] for r in timer.records],
                 [out.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in layer.parameters() if p.grad is not None])
 

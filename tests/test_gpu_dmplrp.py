@@ -47,13 +47,9 @@ def _bare_graph(d):
 
 def _tags(fn):
     from dummynode4graphlearning_amd import ops
-    old = ops.kernel_timer
-    ops.kernel_timer = ops.KernelTimer()
-    try:
+    with ops.KernelTimer() as timer:
         res = fn()
-        return res, set(ops.kernel_timer.summary())
-    finally:
-        ops.kernel_timer = old
+        return res, set(timer.summary())
 
 
 class _path:

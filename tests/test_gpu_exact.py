@@ -119,13 +119,9 @@ class Case:
         for q in layer.parameters():
             q.grad = None
         x = self.x.to(self.dtype).clone().requires_grad_(True)
-        timer = ops.KernelTimer()
-        ops.kernel_timer = timer
-        try:
+        with ops.KernelTimer() as timer:
             out, _ = layer(g, x, self.et)
             out.backward(self.coef.to(self.dtype))
-        finally:
-            ops.kernel_timer = None
         return [r[0] for r in timer.records], out, x.grad, {k: v.grad for k, v in layer.named_parameters()}
 
     def check(self, got, what=""):
@@ -398,13 +394,9 @@ def test_fp32_rep_net_residual_in_the_launches():
                 raise X.PremiseError("a gradient operand holds %d significant bits" % X.sig_bits(gt))
         X.check_premise(X.layer_bounds(t.detach(), src, dst, et, p, R, o.grad), "f32")
     x = x0.clone().requires_grad_(True)
-    timer = ops.KernelTimer()
-    ops.kernel_timer = timer
-    try:
+    with ops.KernelTimer() as timer:
         out = net(g, x)
         out.backward(coef)
-    finally:
-        ops.kernel_timer = None
     tags = [r[0] for r in timer.records]
     assert tags.count("rows_wgrad_multi") == L, tags
     X.assert_bits(out, h, "output")
@@ -489,13 +481,9 @@ def test_linear_any_exact_over_k_and_n(dtype):
             xd = x.to(DEV, dtype).requires_grad_(True)
             wd = w.to(DEV, dtype).requires_grad_(True)
             bd = bias.to(DEV, dtype).requires_grad_(True) if bias is not None else None
-            timer = ops.KernelTimer()
-            ops.kernel_timer = timer
-            try:
+            with ops.KernelTimer() as timer:
                 y = ops.linear_any(xd, wd, bd)
                 y.backward(g.to(DEV, dtype))
-            finally:
-                ops.kernel_timer = None
             assert [r[0] for r in timer.records].count("rows_gemm") == 2
             what = "K=%d N=%d M=%d %s: " % (K, Nn, M, dtype)
             X.assert_bits(y, ref, what + "output")
@@ -648,13 +636,9 @@ def test_neighbor_sum_tile_plan_and_parallel_edges(N, reps):
     with switches(TILE_SUM_ENABLED=True):
         ix = _graph(batch).edge_index()
         xd = x.to(DEV, torch.float32).requires_grad_(True)
-        timer = ops.KernelTimer()
-        ops.kernel_timer = timer
-        try:
+        with ops.KernelTimer() as timer:
             out = ops.neighbor_sum(xd, ix, self_coef=1.0)
             out.backward(gy.to(DEV, torch.float32))
-        finally:
-            ops.kernel_timer = None
         kept = tile and ix.tile_plan() is not None         # (below TILE_SUM_MIN_ROWS the plan is never asked for)
     tags = [r[0] for r in timer.records]
     assert kept == (tile and reps <= 256), (N, reps, kept)

@@ -47,13 +47,9 @@ def _graph(d, dev=DEV):
 
 def _tags(fn):
     from dummynode4graphlearning_amd import ops
-    old = ops.kernel_timer
-    ops.kernel_timer = ops.KernelTimer()
-    try:
+    with ops.KernelTimer() as timer:
         fn()
-        return set(ops.kernel_timer.summary())
-    finally:
-        ops.kernel_timer = old
+        return set(timer.summary())
 
 
 # ------------------------------------------------------------------------------------------------ goldens

@@ -62,12 +62,9 @@ def _run(layer, g, et, x, coef, chain):
 
     timer = ops.KernelTimer()
     with E.switches(LAYER_CHAIN_WGRAD_ENABLED=chain, layer_chain_dgrad=rec_dgrad, mlp_bwd_fused=rec_fused, **LARGE):
-        ops.kernel_timer = timer
-        try:
+        with timer:
             out, _ = layer(g, xs, et)
             out.backward(coef)
-        finally:
-            ops.kernel_timer = None
     tags = [r[0] for r in timer.records]
     assert ("chain_dgrad" in tags) == chain and ("chain_combine" in tags) == chain, tags
     return dict(tags=tags, out=out.detach(), gx=xs.grad.detach(), grads={k: p.grad.detach().clone() for k, p in layer.named_parameters()},
@@ -272,12 +269,9 @@ def _tags(layer, g, et, x, coef, **sw):
     xs = x.clone().requires_grad_(True)
     timer = ops.KernelTimer()
     with E.switches(**sw):
-        ops.kernel_timer = timer
-        try:
+        with timer:
             out, _ = layer(g, xs, et)
             out.backward(coef)
-        finally:
-            ops.kernel_timer = None
     return [r[0] for r in timer.records]
 
 
@@ -301,12 +295,8 @@ def test_dispatch():
     # ... whose input needs no gradient keeps today's launches
     g, et, x, coef = operands(small)
     with E.switches(**ON, **LARGE):
-        timer = ops.KernelTimer()
-        ops.kernel_timer = timer
-        try:
+        with ops.KernelTimer() as timer:
             layer(g, x, et)[0].backward(coef)
-        finally:
-            ops.kernel_timer = None
     assert "chain_dgrad" not in [r[0] for r in timer.records]
     # one graph over 32 nodes: the fold is not absorbed by single-tile units -> today's launches
     big = synthetic.si_uniform_batch(7, 1, 40, 80, 14)

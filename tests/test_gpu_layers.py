@@ -268,13 +268,9 @@ def test_two_layer_fp32_mlp_takes_the_chain_launches(H, slope):
         for l in lins:
             l.zero_grad()
         x = x0.clone().requires_grad_(True)
-        timer = ops.KernelTimer()
-        ops.kernel_timer = timer
-        try:
+        with ops.KernelTimer() as timer:
             y = ops.relu_mlp(x, lins, slope)
             y.backward(gout)
-        finally:
-            ops.kernel_timer = None
         return [r[0] for r in timer.records], [y.detach().clone(), x.grad.clone()] + [p.grad.clone() for l in lins for p in l.parameters()]
 
     tags, got = run()
@@ -914,13 +910,9 @@ def test_absorbed_fold_on_tu_shaped_batches_with_graphs_of_1_to_700_nodes(seed):
             for p in layer.parameters():
                 p.grad = None
             x = x0.clone().requires_grad_(True)
-            timer = ops.KernelTimer()
-            ops.kernel_timer = timer
-            try:
+            with ops.KernelTimer() as timer:
                 out, _ = layer(g, x, et)
                 out.backward(coef)
-            finally:
-                ops.kernel_timer = None
             ix = g.row_index(et, R, True).parts[0][2]
             tags = [r[0] for r in timer.records]
             return ix, tags, [out.detach().clone(), x.grad.clone()] + [p.grad.clone() for p in layer.parameters()]

@@ -43,11 +43,8 @@ def _backward(op, slope, bias, need_x, on):
     timer = ops.KernelTimer()
     with fused(on):
         y = ops.relu_mlp(x, lins, slope=slope)
-        ops.kernel_timer = timer
-        try:
+        with timer:
             y.backward(op["g"])
-        finally:
-            ops.kernel_timer = None
     tags = [r[0] for r in timer.records]
     return tags, p["w1"].grad, p["w2"].grad, p["b1"].grad, p["b2"].grad, x.grad
 
@@ -159,11 +156,8 @@ def test_default_threshold_keeps_small_batches_on_three_launches():
             ops.MLP_BWD_FUSED_MIN_ROWS = min_rows
             timer = ops.KernelTimer()
             y = ops.relu_mlp(x, lins)
-            ops.kernel_timer = timer
-            try:
+            with timer:
                 y.backward(op["g"])
-            finally:
-                ops.kernel_timer = None
             tags = [r[0] for r in timer.records]
             assert tags.count("mlp_bwd_fused") == want and tags.count("rows_wgrad") == 2 - want, (min_rows, tags)
     finally:

@@ -89,13 +89,9 @@ def run_gpu(c, score, give_max=True):
 
 def _tags(fn):
     from dummynode4graphlearning_amd import ops
-    old = ops.kernel_timer
-    ops.kernel_timer = ops.KernelTimer()
-    try:
+    with ops.KernelTimer() as timer:
         res = fn()
-        return res, set(ops.kernel_timer.summary())
-    finally:
-        ops.kernel_timer = old
+        return res, set(timer.summary())
 
 
 FUSED_TAGS = {"seg_attn_fwd", "seg_attn_bwd_q", "seg_attn_bwd_kv"}

@@ -92,13 +92,9 @@ def test_model_matches_the_reference_goldens(name, exact, fused):
 
 def _tags(fn):
     from dummynode4graphlearning_amd import ops
-    old = ops.kernel_timer
-    ops.kernel_timer = ops.KernelTimer()
-    try:
+    with ops.KernelTimer() as timer:
         fn()
-        return set(ops.kernel_timer.summary())
-    finally:
-        ops.kernel_timer = old
+        return set(timer.summary())
 
 
 def _fused_tags(name):

@@ -85,13 +85,9 @@ def test_model_matches_the_reference_goldens(name, exact):
 
 def _tags(fn):
     from dummynode4graphlearning_amd import ops
-    old = ops.kernel_timer
-    ops.kernel_timer = ops.KernelTimer()
-    try:
+    with ops.KernelTimer() as timer:
         fn()
-        return set(ops.kernel_timer.summary())
-    finally:
-        ops.kernel_timer = old
+        return set(timer.summary())
 
 
 def test_path_tags_show_the_ragged_head_and_the_fallback():

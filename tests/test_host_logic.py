@@ -279,3 +279,69 @@ def test_wide_layer_chunks_cover_the_virtual_rows_in_one_round():
         conv_step = int((ch[:cp[R + 1], 2] - ch[:cp[R + 1], 1]).max())
         dense_step = int((ch[cp[R + 1]:, 2] - ch[cp[R + 1]:, 1]).max())
         assert dense_step % 32 == 0 and dense_step <= max(64, conv_step // 2)
+
+
+# (switch, its reader, the module default the reader falls back to, the switch writing the opposite value into the same slot)
+SWITCHES = [("f32_exact", "f32_mode", "F32_EXACT", None), ("dual_fused", "dual_fused_enabled", "DUAL_FUSED_DEFAULT", "dual_composed"),
+            ("lrp_fused", "lrp_fused_enabled", "LRP_FUSED_DEFAULT", "lrp_composed"),
+            ("lrp_collapsed", "lrp_collapsed_enabled", "LRP_COLLAPSED_DEFAULT", None), ("hgt_fused", "hgt_fused_enabled", "HGT_FUSED_DEFAULT", None),
+            ("attn_fused", "attn_fused_enabled", "ATTN_FUSED_DEFAULT", None), ("wl_fused", "wl_fused_enabled", "WL_FUSED_DEFAULT", None),
+            ("gk_fused", "gk_fused_enabled", "GK_FUSED_DEFAULT", None), ("kwl_fused", "kwl_fused_enabled", "KWL_FUSED_DEFAULT", None),
+            ("k3wl_fused", "k3wl_fused_enabled", "K3WL_FUSED_DEFAULT", None)]
+
+
+@pytest.mark.parametrize("switch,reader,default,inverse", SWITCHES, ids=[s[0] for s in SWITCHES])
+def test_thread_switch(monkeypatch, switch, reader, default, inverse):
+    """Every path switch of ops.py: without an override the module default, read when the reader is called (per kernel, and all() of
+    them without a kernel, where the default is a table); nested blocks put back what they found, also when the body raises; the
+    override belongs to the thread that set it and to this switch's slot alone; dual_composed / lrp_composed write the opposite value
+    into the slot of dual_fused / lrp_fused."""
+    import threading
+    from dummynode4graphlearning_amd import ops
+    sw, read = getattr(ops, switch), getattr(ops, reader)
+    others = [getattr(ops, s[1]) for s in SWITCHES if s[0] != switch]
+    rest = [f() for f in others]
+    assert sw.override() is None
+    if isinstance(getattr(ops, default), dict):
+        kernels = list(getattr(ops, default))
+        for mixed in ({k: i == 0 for i, k in enumerate(kernels)}, {k: True for k in kernels}, {k: False for k in kernels}):
+            monkeypatch.setattr(ops, default, mixed)
+            assert [read(k) for k in kernels] == list(mixed.values()) and read() is all(mixed.values())
+            for on in (True, False):
+                with sw(on):                                             # an override wins for every kernel
+                    assert [read(k) for k in kernels] == [on] * len(kernels) and read() is on
+    for dflt in (True, False):
+        if not isinstance(getattr(ops, default), dict):
+            monkeypatch.setattr(ops, default, dflt)
+            assert read() is dflt
+        base = read()
+        for on in (True, False):
+            with sw(on) as outer:
+                assert outer.on is on and read() is on and sw.override() is on
+                assert [f() for f in others] == rest                     # no other switch moves
+                with sw(not on):
+                    assert read() is (not on)
+                assert read() is on
+                with pytest.raises(KeyError):
+                    with sw(not on):
+                        assert read() is (not on)
+                        raise KeyError("body")
+                assert read() is on
+                seen = []
+                t = threading.Thread(target=lambda: seen.extend([read(), sw.override()]))
+                t.start()
+                t.join()
+                assert seen == [base, None]                              # another thread: the default
+                if inverse is not None:
+                    inv = getattr(ops, inverse)
+                    assert issubclass(inv, sw)
+                    with inv(on):
+                        assert read() is (not on) and sw.override() is (not on)
+                    assert read() is on
+                    with inv(not on):
+                        assert read() is on
+            assert read() is base and sw.override() is None
+            if inverse is not None:
+                with getattr(ops, inverse)(on):
+                    assert read() is (not on)
+                assert sw.override() is None

@@ -114,12 +114,9 @@ def run_batch(batch, make, a):
             for impl in impls:
                 with _path(impl):
                     times = B.timed(step, a.steps, a.warmup)
-                    old = ops.kernel_timer
-                    ops.kernel_timer = ops.KernelTimer()
-                    step()
-                    tags = {k: round(v[1], 3) for k, v in ops.kernel_timer.summary().items()
-                            if k.startswith(("lrp_", "gather_segsum", "segment"))}
-                    ops.kernel_timer = old
+                    with ops.KernelTimer() as timer:
+                        step()
+                    tags = {k: round(v[1], 3) for k, v in timer.summary().items() if k.startswith(("lrp_", "gather_segsum", "segment"))}
                 print(json.dumps(dict(tool="si_dmplrp_bench", what=what, batch=batch, impl=impl, round=rnd, seq_len=L, H=H,
                                       steps=a.steps, median_ms=statistics.median(times), min_ms=min(times), max_ms=max(times),
                                       kernel_ms=tags)), flush=True)

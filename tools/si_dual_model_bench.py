@@ -232,11 +232,9 @@ def run_one(a, batches):
                comp_opt=a.comp_opt if a.model == "compgcn" else None, nodes=gg.number_of_nodes(), edges=gg.number_of_edges(),
                steps=a.steps, median_ms=statistics.median(times), min_ms=min(times), max_ms=max(times))
     if a.tags:
-        old = ops.kernel_timer
-        ops.kernel_timer = ops.KernelTimer()
-        run(step)
-        out["tags"] = {k: v[0] for k, v in ops.kernel_timer.summary().items()}
-        ops.kernel_timer = old
+        with ops.KernelTimer() as timer:
+            run(step)
+        out["tags"] = {k: v[0] for k, v in timer.summary().items()}
     return out
 
 

@@ -71,11 +71,9 @@ def main():
         for impl in impls:
             with ops.hgt_fused(impl == "fused"):
                 times = B.timed(step, a.steps, a.warmup)
-                old = ops.kernel_timer
-                ops.kernel_timer = ops.KernelTimer()
-                step()
-                tags = {k: round(v[1], 3) for k, v in ops.kernel_timer.summary().items() if k.startswith(TAGS)}
-                ops.kernel_timer = old
+                with ops.KernelTimer() as timer:
+                    step()
+                tags = {k: round(v[1], 3) for k, v in timer.summary().items() if k.startswith(TAGS)}
             all_times[impl] += times
             round_medians[impl].append(statistics.median(times))
             print(json.dumps(dict(tool="si_hgt_bench", what=what, impl=impl, round=rnd, H=H, heads=a.heads, relations=nel,

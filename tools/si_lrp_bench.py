@@ -142,11 +142,9 @@ def main():
         for impl in impls:
             with _path(impl):
                 times = B.timed(step, a.steps, a.warmup)
-                old = ops.kernel_timer
-                ops.kernel_timer = ops.KernelTimer()
-                step()
-                tags = {k: round(v[1], 3) for k, v in ops.kernel_timer.summary().items() if k.startswith(("lrp_", "gather_segsum"))}
-                ops.kernel_timer = old
+                with ops.KernelTimer() as timer:
+                    step()
+                tags = {k: round(v[1], 3) for k, v in timer.summary().items() if k.startswith(("lrp_", "gather_segsum"))}
             print(json.dumps(dict(tool="si_lrp_bench", what="model" if a.model else "layer", impl=impl, round=rnd, seq_len=L, H=H,
                                   nodes=gg.number_of_nodes(), edges=gg.number_of_edges(), steps=a.steps,
                                   median_ms=statistics.median(times), min_ms=min(times), max_ms=max(times), kernel_ms=tags)),
