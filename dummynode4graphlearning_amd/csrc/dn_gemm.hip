@@ -23,6 +23,7 @@ template <typename T> __device__ __forceinline__ float ld(const T* p) { return (
 template <typename T> __device__ __forceinline__ T cvt(float v) { return (T)v; }
 
 // Y[tile rows, n0 : n0 + 64] = A[tile rows, :] @ Wr   with Wr[k][n] = transposed ? W[rel][n][k] : W[rel][k][n]
+// (instantiated for bf16 only: fp32 runs on rows_gemm_mfma_f32_kernel below)
 template <typename T>
 __global__ __launch_bounds__(kThreads) void rows_gemm_kernel(const T* __restrict__ A, const T* __restrict__ W,
                                                              const T* __restrict__ bias, int32_t K, int32_t N,
@@ -255,22 +256,18 @@ int rows_gemm(const T* A, const T* W, const T* bias, int32_t K, int32_t N, int32
     if (num_tiles == 0) return DN_OK;
     DN_REQUIRE(A && W && tiles && Y, "dn_rows_gemm: NULL pointer");
     if constexpr (sizeof(T) == 4) {                                       // fp32: exact-f32 MFMA tiles
-        static const int mfma = dn_knob("DN_GEMM_MFMA", 1);               // tuning build: 0 keeps the FMA tiles
-        if (mfma) {
-            if (K >= 128)
-                hipLaunchKernelGGL(rows_gemm_mfma_f32_kernel<128>, dim3((unsigned)num_tiles, (unsigned)dn_cdiv(N, TN)), dim3(kThreads), 0, st,
-                                   (const float*)A, (const float*)W, (const float*)bias, K, N, transposed,
-                                   reinterpret_cast<const Piece*>(tiles), (float*)Y);
-            else
-                hipLaunchKernelGGL(rows_gemm_mfma_f32_kernel<32>, dim3((unsigned)num_tiles, (unsigned)dn_cdiv(N, TN)), dim3(kThreads), 0, st,
-                                   (const float*)A, (const float*)W, (const float*)bias, K, N, transposed,
-                                   reinterpret_cast<const Piece*>(tiles), (float*)Y);
-            DN_CHECK_LAUNCH();
-            return DN_OK;
-        }
+        if (K >= 128)
+            hipLaunchKernelGGL(rows_gemm_mfma_f32_kernel<128>, dim3((unsigned)num_tiles, (unsigned)dn_cdiv(N, TN)), dim3(kThreads), 0, st,
+                               (const float*)A, (const float*)W, (const float*)bias, K, N, transposed,
+                               reinterpret_cast<const Piece*>(tiles), (float*)Y);
+        else
+            hipLaunchKernelGGL(rows_gemm_mfma_f32_kernel<32>, dim3((unsigned)num_tiles, (unsigned)dn_cdiv(N, TN)), dim3(kThreads), 0, st,
+                               (const float*)A, (const float*)W, (const float*)bias, K, N, transposed,
+                               reinterpret_cast<const Piece*>(tiles), (float*)Y);
+    } else {                                                              // bf16: FMA tiles
+        hipLaunchKernelGGL((rows_gemm_kernel<T>), dim3((unsigned)num_tiles, (unsigned)dn_cdiv(N, TN)), dim3(kThreads), 0, st, A, W, bias, K,
+                           N, transposed, reinterpret_cast<const Piece*>(tiles), Y);
     }
-    hipLaunchKernelGGL((rows_gemm_kernel<T>), dim3((unsigned)num_tiles, (unsigned)dn_cdiv(N, TN)), dim3(kThreads), 0, st, A, W, bias, K,
-                       N, transposed, reinterpret_cast<const Piece*>(tiles), Y);
     DN_CHECK_LAUNCH();
     return DN_OK;
 }

@@ -269,14 +269,15 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_multi_kernel(WgJobs job
 //     s_waitcnt vmcnt(GL * (NST - 2)) followed by ONE raw s_barrier per tile (never __syncthreads(): its fence would
 //     drain the ring).  Rows past the end of the chunk read a zero row, tiles past the end are issued as zero tiles so
 //     the count stays static; the ring is drained (vmcnt(0)) before the LDS is reused or the workgroup ends.
-//   * used when no ReLU mask is folded in (maskA == NULL); H in {128, 256} (64-row stages at H = 128: same bytes per stage).
+//   * used when no ReLU mask is folded in (maskA == NULL), at H = 256 only (where the register-staged kernel is pinned at one
+//     workgroup per CU by its 128 accumulator VGPRs; at H = 128 it fits two and is ~3 % faster than a ring: 1.95 vs 2.01 ms per step).
 // -------------------------------------------------------------------------------------------------
 __device__ __attribute__((aligned(16))) uint4 g_zero_row[64];        // 1 KiB of zeros (device globals are zero-initialised)
 
 #ifndef DN_WGM_ABL
 #define DN_WGM_ABL 0        // diagnostic builds (DN_BUILD_EXTRA=-DDN_WGM_ABL=n): 1 no mask pass, 2 mask bits from the zero row
 #endif
-template <int H, bool MASKED, bool DENSE>
+template <bool MASKED, bool DENSE>
 __global__ __launch_bounds__(kWgThreads) void rows_wgrad_dma_kernel(const bf16_t* __restrict__ A,
                                                                     const bf16_t* __restrict__ A2, int32_t na1,
                                                                     const int32_t* __restrict__ ia,
@@ -287,16 +288,16 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_dma_kernel(const bf16_t
                                                                     float* __restrict__ partial, int32_t colsum_arg,
                                                                     float* __restrict__ colsum_partial,
                                                                     const uint8_t* __restrict__ maskBits, float slope) {
-    static_assert(H == 256 || H == 128, "unsupported width");
-    constexpr int TR = (H == 256) ? 32 : 64;       // rows per stage: 32 KiB per stage at either width (1 or 2 MFMA K-steps)
+    constexpr int H = 256;
+    constexpr int TR = 32;                         // rows per stage: 32 KiB per stage (one MFMA K-step)
     constexpr int NST = 4;                         // ring stages (128 KiB)
     constexpr int ROWB = 2 * H;                    // bytes per row
     constexpr int MATB = TR * ROWB;                // bytes per operand per stage
     constexpr int BITB = MASKED ? 1024 : 0;        // per stage: the tile's ReLU-mask bits (TR rows x H/8 bytes = 1 KiB)
     constexpr int STB = 2 * MATB + BITB;
     constexpr int LPRW = H / 8;                    // lanes (16-byte pieces) per row
-    constexpr int RPI = 64 / LPRW;                 // rows per DMA wave-instruction (2 or 4)
-    constexpr int RW = TR / 8;                     // rows of each operand a wave stages per tile (4 or 8)
+    constexpr int RPI = 64 / LPRW;                 // rows per DMA wave-instruction (2)
+    constexpr int RW = TR / 8;                     // rows of each operand a wave stages per tile (4)
     constexpr int PPW = RW / RPI;                  // DMA instructions per wave, operand and tile
     constexpr int GL = 2 * PPW;                    // DMA instructions per wave and tile (+ 1 on the wave that fetches a tile's mask bits)
     constexpr int MT = H / 2 / 16, NT = H / 4 / 16;
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_dma_kernel(const bf16_t
             if constexpr (DENSE) {
                 // no index, no second source (the MLP's weight gradients): row p of both operands, or the zero row past the
                 // chunk's end -- one 64-bit multiply-add and one select per operand instead of the general path's ~25
-                // instructions per DMA pair (what the issue phase of these launches costs is this arithmetic: see rows_wgrad_ix_kernel)
+                // instructions per DMA pair (what the issue phase of these launches costs is this arithmetic: docs/LAB_NOTES.md, round 4)
                 const int p = ch.beg + T * TR + rl;
                 const bool okp = p < ch.end;
                 const uint64_t off = (uint64_t)(uint32_t)p * ROWB + (uint64_t)gch;
@@ -418,7 +419,7 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_dma_kernel(const bf16_t
         return __builtin_bit_cast(bf16x8, f);
     };
     float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    constexpr int CPT = TR * LPRW / kWgThreads;                            // column-sum pieces per thread and tile (2 or 1)
+    constexpr int CPT = TR * LPRW / kWgThreads;                            // column-sum pieces per thread and tile (2)
     const int cchunk = tid % LPRW, crow = tid / LPRW;
 
     // ---- prologue: NST-1 tiles in flight (chunk tables never hold empty chunks; guard anyway: pe must be a valid row) ----
@@ -478,14 +479,13 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_dma_kernel(const bf16_t
         load_idx(t + NST);
         char* sA = lds + (t % NST) * STB;
         const char* sG = sA + MATB;
-#pragma unroll
-        for (int kk = 0; kk < TR / 32; ++kk) {
+        {
             bf16x8 fb[NT];
 #pragma unroll
-            for (int n = 0; n < NT; ++n) fb[n] = frag(sG + kk * 32 * ROWB, wn * NT + n);
+            for (int n = 0; n < NT; ++n) fb[n] = frag(sG, wn * NT + n);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-                const bf16x8 fa = frag(sA + kk * 32 * ROWB, wm * MT + m);
+                const bf16x8 fa = frag(sA, wm * MT + m);
 #pragma unroll
                 for (int n = 0; n < NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[n], acc[m][n], 0, 0, 0);
             }
@@ -539,254 +539,18 @@ __global__ __launch_bounds__(kWgThreads) void rows_wgrad_dma_kernel(const bf16_t
 }
 
 // -------------------------------------------------------------------------------------------------
-// rows_wgrad_ix_kernel: the LDS-DMA ring above for GATHERED operands (both index arrays given; H = 256; the conv's weight
-// gradient), with the per-tile bookkeeping moved off the scalar unit.  In the kernel above every wave fetches its 8 row indices
-// with scalar loads right before the fragment reads, and the `s_waitcnt lgkmcnt(0)` in front of the first MFMA (SMEM shares the
-// counter with LDS) waits for them: ~2,400-2,900 cycles per 32-row tile against 1,024 of MFMA, from L2 as from HBM.  Here a
-// wave's 8 indices of a tile arrive as ONE 8-lane LDS-DMA two tiles ahead of their use (into a small per-wave LDS ring), the
-// row addresses are picked with selects instead of exec-masked branches, and nothing in the loop touches SMEM.
-// vmcnt arithmetic: a wave issues per tile [index DMA] [4 row DMAs], in this order.  (Walking the rows in the L2-blocked sweep order
-// with one partial product per run of tiles was built on top of this kernel and measured: 1.1 GB fewer HBM reads per launch, the same
-// time -- docs/LAB_NOTES.md, round 3.)
-// -------------------------------------------------------------------------------------------------
-#ifdef DN_WG_STATS
-// diagnostic build (-DDN_WG_STATS): shader-clock cycles of the last launch per workgroup, waves 0 (issues its DMAs first) and 4
-// (multiplies first): {loop, wait + barrier, DMA issue, fragments + MFMAs + column sums}, and the loop's wall ticks (100 MHz)
-__device__ unsigned long long g_wg_stats[256][2][5];
-#define DN_WG_STAMP() __builtin_amdgcn_s_memtime()
-#define DN_WG_STAT(var, expr) var += (expr)
-#else
-#define DN_WG_STAMP() 0ull
-#define DN_WG_STAT(var, expr)
-#endif
-__global__ __launch_bounds__(kWgThreads) void rows_wgrad_ix_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ A2,
-                                                                   int32_t na1, const int32_t* __restrict__ ia,
-                                                                   const bf16_t* __restrict__ G, const bf16_t* __restrict__ G2,
-                                                                   int32_t ng1, const int32_t* __restrict__ ig,
-                                                                   const Chunk* __restrict__ chunks, float* __restrict__ partial,
-                                                                   int32_t colsum_arg, float* __restrict__ colsum_partial) {
-    constexpr int H = 256, TR = 32, NST = 4, ROWB = 2 * H, MATB = TR * ROWB, STB = 2 * MATB;
-    constexpr int LPRW = H / 8, RW = TR / 8;       // 32 lanes per row; 4 rows of each operand per wave and tile
-    constexpr int MT = H / 2 / 16, NT = H / 4 / 16;
-    constexpr int kSlots = 8;                      // per-wave ring of index octets
-    constexpr int kOps = 5;                        // vector-memory operations a wave issues per tile
-    __shared__ __attribute__((aligned(1024))) char lds[NST * STB];
-    __shared__ __attribute__((aligned(32))) int32_t idxL[8][kSlots][8];       // {ia[p0..p0+3], ig[p0..p0+3]} of a wave's rows
-    const unsigned lds_base = lds_addr(lds);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const Chunk ch = chunks[blockIdx.x];
-    const int32_t colsum_all = colsum_arg & 0xff, colsum_of = colsum_for(colsum_arg, ch.rel);
-    const int ntiles = (ch.end - ch.beg + TR - 1) / TR;
-    const int32_t ch_beg = ch.beg, ch_end = ch.end;
-    const char* zero = reinterpret_cast<const char*>(g_zero_row);
-    const unsigned idx_base = lds_addr(&idxL[wave][0][0]);
-
-    // {first row of my 4, last row of the tile, live} of tile T (wave-uniform values; tiles past the end repeat the last one)
-    auto tile_rows = [&](int T, int& p0, int& pe, bool& live) {
-        live = T < ntiles;
-        const int Tc = min(T, ntiles - 1);
-        p0 = ch_beg + Tc * TR + RW * wave;
-        pe = min(ch_beg + Tc * TR + TR, ch_end) - 1;
-    };
-    // The index octet of a wave and tile sits in the ring as {ia0, ia2, ig0, ig2, ia1, ia3, ig1, ig3} (rows p0 .. p0 + 3 of the wave):
-    // the four values a lane needs for its two DMA pairs -- rows rin and 2 + rin of both operands -- are ONE 16-byte LDS read.
-    auto dma_idx = [&](int T) {                    // lanes 0..7 fetch one index each (lane l lands at + 4 l)
-        int p0, pe;
-        bool live;
-        tile_rows(T, p0, pe, live);
-        const int row = (lane >> 2) + 2 * (lane & 1);                      // lane l: row (l >> 2) + 2 (l & 1) of ia (l & 2 clear) / ig
-        const int pc = max(min(p0 + row, pe), 0);
-        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(idx_base + (unsigned)(T % kSlots) * 32u));
-        if (lane < 8) glds4(((lane & 2) ? ig : ia) + pc, dst);
-    };
-    const int rin = lane / LPRW, cpos = lane % LPRW;
-    // Address of a row = base + index * 512 (+ the second source's displacement for indices >= n1): one 64-bit multiply-add, one
-    // compare and one 64-bit select.  (Round 3's form -- compare, base select, subtract, shift, add, zero-row select per operand
-    // behind two dependent LDS reads and two exec-masked regions -- was ~230 of a tile's ~790 timer ticks per wave: the address
-    // arithmetic, not the DMA instructions, is what the issue phase cost; ablations in docs/LAB_NOTES.md, round 4.)
-    const uint64_t dA = (uint64_t)(uintptr_t)A2 - (uint64_t)(uintptr_t)A - (uint64_t)(uint32_t)na1 * ROWB;   // (A2 == NULL: never selected)
-    const uint64_t dG = (uint64_t)(uintptr_t)G2 - (uint64_t)(uintptr_t)G - (uint64_t)(uint32_t)ng1 * ROWB;
-    int gch2[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int rl = RW * wave + 2 * j + rin;                            // row of the stage this lane fills
-        const int f = (rl & 3) | (((rl >> 3) & 1) << 2);
-        gch2[j] = ((((cpos >> 1) ^ f) << 1) | (cpos & 1)) * 16;             // source byte offset inside the row
-    }
-    auto issue = [&](int T) {                      // the 4 row DMAs of tile T (indices of tile T have landed)
-        int p0, pe;
-        bool live;
-        tile_rows(T, p0, pe, live);
-        const i32x4 iv = *reinterpret_cast<const i32x4*>(&idxL[wave][T % kSlots][4 * rin]);   // {ia[k], ia[2 + k], ig[k], ig[2 + k]}, k = rin
-        const unsigned st = lds_base + (unsigned)(T % NST) * STB;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int k = 2 * j + rin;                                     // my row of the wave's 4
-            // rows past the chunk's end (and whole tiles past it): G reads the zero row, so the pair adds nothing; A repeats the
-            // chunk's last row (the index was clamped), unless its column sums are wanted -- then it reads the zero row too
-            const bool ok = live && p0 + k <= pe;
-            const int32_t ra = iv[j], rg = iv[2 + j];
-            uint64_t pa = (uint64_t)(uintptr_t)A + (uint64_t)(uint32_t)ra * ROWB + (ra >= na1 ? dA : 0ull);
-            uint64_t pg = (uint64_t)(uintptr_t)G + (uint64_t)(uint32_t)rg * ROWB + (rg >= ng1 ? dG : 0ull);
-            pg = ok ? pg : (uint64_t)(uintptr_t)zero;
-            if (colsum_of == 1) pa = ok ? pa : (uint64_t)(uintptr_t)zero;  // (wave-uniform condition)
-            const unsigned da = st + (unsigned)(RW * wave + 2 * j) * ROWB;  // wave-uniform; lane l lands at + 16 l
-#if defined(DN_WG_STATS) && defined(DN_WG_ABL)
-            if (DN_WG_ABL & 1) { asm volatile("" :: "v"(pa), "v"(pg)); continue; }                       // (ablation: address math, no DMAs)
-            if (DN_WG_ABL & 2) { glds16(zero + lane * 16, da); glds16(zero + lane * 16, da + MATB); continue; }   // (DMAs from one row, no math)
-#endif
-            glds16(reinterpret_cast<const char*>(pa + (uint64_t)gch2[j]), da);
-            glds16(reinterpret_cast<const char*>(pg + (uint64_t)gch2[j]), da + MATB);
-        }
-    };
-
-    // ---- MFMA side (as in rows_wgrad_dma_kernel) ----------------------------------------------------------------
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int fg = lane >> 4, fq = (lane & 15) >> 2, fp = lane & 3;
-    const int fsw = fq | ((fg & 1) << 2);
-    const int frow = (8 * fg + fq) * ROWB + 8 * fp;
-    typedef short4v __attribute__((address_space(3))) * lds_p;
-    auto frag = [&](const char* mat, int slot) -> bf16x8 {
-        const char* a0 = mat + frow + ((slot ^ fsw) << 5);
-        const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0));
-        const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(a0 + 4 * ROWB));
-        const short8v f = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(bf16x8, f);
-    };
-    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    constexpr int CPT = TR * LPRW / kWgThreads;                            // column-sum pieces per thread and tile (2)
-    const int cchunk = tid % LPRW, crow = tid / LPRW;
-    auto flush = [&](int slab) {                   // one partial product (+ its column sums) out to workspace slab `slab`; sums restart
-        float* out = partial + (size_t)slab * H * H;
-        const int k0 = wm * (H / 2), n0 = wn * (H / 4);
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int k = k0 + m * 16 + (lane >> 4) * 4 + i, c = n0 + n * 16 + (lane & 15);
-                    out[(size_t)k * H + c] = acc[m][n][i];
-                }
-                acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-    };
-
-    // ---- prologue --------------------------------------------------------------------------------------------------
-    if (ntiles <= 0) {
-        for (int i = tid; i < H * H; i += kWgThreads) partial[(size_t)blockIdx.x * H * H + i] = 0.f;
-        if (colsum_all != 0 && tid < H) colsum_partial[(size_t)blockIdx.x * H + tid] = 0.f;
-        return;
-    }
-#pragma unroll 1
-    for (int T = 0; T < 5; ++T) dma_idx(T);
-    wait_vmcnt<0>();
-#pragma unroll 1
-    for (int T = 0; T < NST - 1; ++T) issue(T);
-    wait_vmcnt<8>();                                                       // tile 0 has landed (the loop's count starts at tile 1)
-    const bool dma_first = wave < 4;
-    unsigned long long st_bar = 0, st_dma = 0, st_mm = 0;
-    const unsigned long long l0 = DN_WG_STAMP();
-#ifdef DN_WG_STATS
-    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#pragma unroll 1
-    for (int t = 0; t < ntiles; ++t) {
-        const unsigned long long a0 = DN_WG_STAMP();
-        // issued after the index octet of tile t+3 (two tiles ago): its tile's 4 row DMAs and last tile's kOps operations
-        wait_vmcnt<kOps + 4>();                                            // rows of tile t, indices of tile t+3
-        __builtin_amdgcn_s_barrier();                                      // everyone's have; stage of tile t-1 is free
-        const unsigned long long a1 = DN_WG_STAMP();
-        DN_WG_STAT(st_bar, a1 - a0);
-        // the two waves of a SIMD (w and w + 4) take turns: one issues its DMAs while the other multiplies (issuing a DMA costs a
-        // wave 100-185 cycles; in lock step the SIMD's matrix pipe would idle through both waves' issue phases)
-        if (dma_first) {
-            dma_idx(t + 5);
-            issue(t + NST - 1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned long long a2 = DN_WG_STAMP();
-        if (dma_first) DN_WG_STAT(st_dma, a2 - a1);
-        char* sA = lds + (t % NST) * STB;
-        const char* sG = sA + MATB;
-        {
-            bf16x8 fb[NT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) fb[n] = frag(sG, wn * NT + n);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                const bf16x8 fa = frag(sA, wm * MT + m);
-#pragma unroll
-                for (int n = 0; n < NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[n], acc[m][n], 0, 0, 0);
-            }
-        }
-        if (colsum_of != 0) {
-            const char* M = colsum_of == 1 ? sA : sG;
-#pragma unroll
-            for (int j = 0; j < CPT; ++j) {
-                const int r = crow + j * (kWgThreads / LPRW);
-                const int f = (r & 3) | (((r >> 3) & 1) << 2);
-                const int pos = (((cchunk >> 1) ^ f) << 1) | (cchunk & 1);
-                const uint4 v = *reinterpret_cast<const uint4*>(M + r * ROWB + pos * 16);
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    cs[2 * i] += __uint_as_float(w[i] << 16);
-                    cs[2 * i + 1] += __uint_as_float(w[i] & 0xffff0000u);
-                }
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned long long a3 = DN_WG_STAMP();
-        DN_WG_STAT(st_mm, a3 - a2);
-        if (!dma_first) {
-            dma_idx(t + 5);
-            issue(t + NST - 1);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // my LDS reads of tile t are done before the next barrier
-        if (!dma_first) DN_WG_STAT(st_dma, DN_WG_STAMP() - a3);
-    }
-#ifdef DN_WG_STATS
-    if ((wave == 0 || wave == 4) && lane == 0 && blockIdx.x < 256) {
-        unsigned long long* o = g_wg_stats[blockIdx.x][wave >> 2];
-        o[0] = DN_WG_STAMP() - l0; o[1] = st_bar; o[2] = st_dma; o[3] = st_mm; o[4] = __builtin_amdgcn_s_memrealtime() - rt0;
-    }
-#endif
-    wait_vmcnt<0>();                                                       // drain what is still in flight
-    __builtin_amdgcn_s_barrier();
-    flush((int)blockIdx.x);
-    if (colsum_all != 0) {
-        constexpr int TPC = kWgThreads / LPRW;
-        float* red = reinterpret_cast<float*>(lds);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) red[crow * H + cchunk * 8 + i] = cs[i];
-        __syncthreads();
-        if (tid < H) {
-            float sum = 0.f;
-            for (int sl = 0; sl < TPC; ++sl) sum += red[sl * H + tid];
-            colsum_partial[(size_t)blockIdx.x * H + tid] = sum;
-        }
-    }
-}
-
-// -------------------------------------------------------------------------------------------------
-// rows_wgrad_ls_kernel ("loader-specialised", H = 256): the ring of the two kernels above with the ROLES of a tile's work on
+// rows_wgrad_ls_kernel ("loader-specialised", H = 256): the ring of the kernel above with the ROLES of a tile's work on
 // separate waves, as in the ring transform (dn_rel_ring.hip): 12 waves per workgroup, 3 per SIMD --
 //   * waves 8..11 (loaders) issue every LDS-DMA of a tile (8 rows of each operand per loader, the index octets two groups ahead
 //     through a per-wave LDS ring), apply the activation mask to a landed tile in place (MODE 2) and take the column sums;
 //   * waves 0..7 (compute) do nothing but fragment reads and MFMAs (128 x 64 of the 256 x 256 product each, as above).
-// Why: with the rows cache-resident (indices folded into 1 MB, tools/wgrad_local_exp.py) the kernels above still need 1.09 us per
-// tile and workgroup against 0.49 of MFMA work -- every wave's tile was [wait, barrier, 4-5 DMA issues at 60-185 cycles each +
+// Why: with the rows cache-resident (indices folded into 1 MB, tools/wgrad_local_exp.py) the eight-wave rings still needed 1.09 us
+// per tile and workgroup against 0.49 of MFMA work -- every wave's tile was [wait, barrier, 4-5 DMA issues at 60-185 cycles each +
 // their address arithmetic, 24 fragment reads, 32 MFMAs, column sums], two such streams per SIMD; the launch was bound by its
 // own instruction stream (docs/LAB_NOTES.md, round 6), which is why neither fewer HBM bytes nor cache residency made it faster.
 // Same tiles in the same order, the same MFMA per tile and accumulator, the same partition of the column sums: results are
-// bit-identical to the kernels above.
+// bit-identical to the kernel above.  (The eight-wave ring for gathered operands, rows_wgrad_ix_kernel, is retired: see
+// "Retired kernel generations" in docs/LAB_NOTES.md for the commit that still has it.)
 //   MODE 0: gathered operands (both index arrays; second sources A2 / G2), 1: both operands in row order, 2: row order + the A
 //   operand masked by bits (dn_rows_wgrad_bf16's maskBits).
 // vmcnt: a loader issues per tile ONE group, [index octet of tile s + 7] [8 row pieces of tile s + 3] behind barrier s (MODE 0;
@@ -799,6 +563,16 @@ constexpr int kLsCompute = 8, kLsLoaders = 4, kLsThreads = 64 * (kLsCompute + kL
 // rings.  ch: the workgroup's chunk with rows and relation LOCAL to the job (a multi-job launch lays the jobs' rows end to end:
 // row0 = where this job's begin in the chunk table, vrel = the chunk's relation as the table and chunk_ptr number it).
 constexpr int kLsStageBytes = 2 * 32 * 512, kLsStages = 4, kLsSlots = 8;
+#ifdef DN_WG_STATS
+// diagnostic build (-DDN_WG_STATS): shader-clock cycles of the last launch per workgroup, [0] compute wave 0: {loop, barrier waits,
+// 0, 0, the loop's wall ticks (100 MHz)}, [1] loader wave 8: {loop, vmcnt waits, barrier waits, DMA issue, column sums}
+__device__ unsigned long long g_wg_stats[256][2][5];
+#define DN_WG_STAMP() __builtin_amdgcn_s_memtime()
+#define DN_WG_STAT(var, expr) var += (expr)
+#else
+#define DN_WG_STAMP() 0ull
+#define DN_WG_STAT(var, expr)
+#endif
 template <int MODE>
 __device__ __forceinline__ void wgrad_ls_body(const bf16_t* __restrict__ A, const bf16_t* __restrict__ A2,
                                               int32_t na1, const int32_t* __restrict__ ia,
@@ -844,7 +618,7 @@ __device__ __forceinline__ void wgrad_ls_body(const bf16_t* __restrict__ A, cons
         return;
     }
     // column sums: loader thread lt stands for the two threads (crow = lt / 32 and 8 + lt / 32, chunk lt % 32) of the 512-thread
-    // kernels above -- rows crow, crow + 16 of every tile, in this order
+    // kernel above -- rows crow, crow + 16 of every tile, in this order
     float cs[2][8];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -1166,7 +940,8 @@ __global__ __launch_bounds__(kLsThreads) void rows_wgrad_ls_kernel(const bf16_t*
                                                                    int32_t colsum_arg, float* __restrict__ colsum_partial,
                                                                    const uint8_t* __restrict__ maskBits, float slope,
                                                                    const int32_t* __restrict__ chunk_ptr) {
-    __shared__ __attribute__((aligned(1024))) char lds[kLsStages * (kLsStageBytes + (MODE == 2 ? 1024 : 0))];
+    static_assert(MODE == 0 || MODE == 1, "MODE 2 runs in rows_wgrad_ls_multi_kernel only (a single launch: rows_wgrad_dma_kernel)");
+    __shared__ __attribute__((aligned(1024))) char lds[kLsStages * kLsStageBytes];
     __shared__ __attribute__((aligned(64))) int32_t idxL[MODE == 0 ? kLsLoaders : 1][kLsSlots][16];
     __shared__ __attribute__((aligned(128))) uint64_t adrL[kLsLoaders][kLsSlots][16];   // per loader and tile: the 16 row addresses
     const Chunk ch = chunks[blockIdx.x];
@@ -1222,6 +997,8 @@ __global__ __launch_bounds__(kLsThreads) void rows_wgrad_ls_multi_kernel(WgJobs 
 constexpr int kTfThreads = 512;   // 8 waves, each owning HO/8 output columns
 constexpr int kTfRows = 32;
 
+// D = gathered tiles in flight.  Only D = 1 is instantiated (2 .. 4 measured no faster and are retired: docs/LAB_NOTES.md).  The
+// parameter and its loops stay in the source for now: written without them all three widths compile to a different prologue.
 template <int HI, int HO, int D>
 __global__ __launch_bounds__(kTfThreads, (D == 1 ? 4 : 2)) void rows_transform_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ X2, int32_t n1, const int32_t* __restrict__ idx,
@@ -1827,10 +1604,6 @@ int launch_chain2(const bf16_t* X, const bf16_t* W1n, const bf16_t* b1, const bf
     return DN_OK;
 }
 
-static int tf_depth() {
-    static const int d = [] { const int v = dn_knob("DN_TF_DEPTH", 1); return (v >= 1 && v <= 4) ? v : 1; }();
-    return d;
-}
 static int tf_wg_per_cu() {
     static const int d = dn_knob("DN_TF_WGS", 0);
     return d;
@@ -1841,7 +1614,6 @@ int launch_transform(const bf16_t* X, const bf16_t* X2, int32_t n1, const int32_
                      int32_t relu, float slope, const bf16_t* mask_pos, const Chunk* tiles, int64_t num_tiles, bf16_t* Y, hipStream_t st,
                      int32_t w_kn = 0) {
     // contiguous tile ranges keep a workgroup inside one relation most of the time
-    const int depth = tf_depth();
     // streaming (non-temporal) stores of the output rows: they are re-read only after ~1 GB of other traffic, so keeping
     // them out of L2 / Infinity Cache is worth 1.5-2 % of the step (DN_NT=0 turns it off: bit 0 transform, bit 1 selfsum)
     static const int nt = dn_knob("DN_NT", 3);
@@ -1851,18 +1623,12 @@ int launch_transform(const bf16_t* X, const bf16_t* X2, int32_t n1, const int32_
     relu |= w_kn ? 32 : 0;
     // workgroups per CU: a tile is 32 rows x 2*HI bytes, so narrower rows need more workgroups in flight to keep the same
     // bytes per CU outstanding (H = 128: 64 VGPRs, 26 KB LDS -> 4 fit; measured 2.24 -> 2.07 ms per step at H = 128)
-    const int64_t per_cu = tf_wg_per_cu() > 0 ? tf_wg_per_cu() : (depth == 1 ? (HI <= 128 ? 4 : 2) : 1);
+    const int64_t per_cu = tf_wg_per_cu() > 0 ? tf_wg_per_cu() : (HI <= 128 ? 4 : 2);
     const int64_t max_wg = 256 * per_cu;
     const int64_t tiles_per_wg = dn_cdiv(num_tiles, max_wg);
     const int64_t grid = dn_cdiv(num_tiles, tiles_per_wg);
-#define DN_TF_LAUNCH(DEPTH)                                                                                                  \
-    hipLaunchKernelGGL((rows_transform_kernel<HI, HO, DEPTH>), dim3((unsigned)grid), dim3(kTfThreads), 0, st, X, X2, n1, idx, \
-                       Wn, bias, relu, slope, mask_pos, tiles, (int32_t)num_tiles, (int32_t)tiles_per_wg, Y)
-    if (depth == 1) DN_TF_LAUNCH(1);
-    else if (depth == 2) DN_TF_LAUNCH(2);
-    else if (depth == 3) DN_TF_LAUNCH(3);
-    else DN_TF_LAUNCH(4);
-#undef DN_TF_LAUNCH
+    hipLaunchKernelGGL((rows_transform_kernel<HI, HO, 1>), dim3((unsigned)grid), dim3(kTfThreads), 0, st, X, X2, n1, idx, Wn, bias,
+                       relu, slope, mask_pos, tiles, (int32_t)num_tiles, (int32_t)tiles_per_wg, Y);
     DN_CHECK_LAUNCH();
     return DN_OK;
 }
@@ -1922,71 +1688,42 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
 }
 
-// DN_WGRAD_DMA: 0 = never, 1 (default) = at H = 256 (where the register-staged kernel is pinned at one workgroup per CU by
-// its 128 accumulator VGPRs), 2 = at H = 128 too (there the register-staged kernel fits two workgroups per CU and is
-// ~3 % faster than the ring: 1.95 vs 2.01 ms per step)
-int wgrad_dma_mode() {
-    static const int mode = dn_knob("DN_WGRAD_DMA", 1);
-    return mode;
-}
-
-int wgrad_ix_mode() {                              // tuning build: DN_WGRAD_IX=0 keeps the scalar-index ring for gathered operands
-    static const int mode = dn_knob("DN_WGRAD_IX", 1);
-    return mode;
-}
-
 int wgrad_il_mode() {                              // tuning build: DN_WGRAD_IL=0 keeps a relation's chunks contiguous
     static const int mode = dn_knob("DN_WGRAD_IL", 1);
     return mode;
 }
 
-// DN_WGRAD_LS (tuning build): bit 0 gathered operands, bit 1 row order, bit 2 row order + mask bits on rows_wgrad_ls_kernel
-int wgrad_ls_mode() {
-    static const int mode = dn_knob("DN_WGRAD_LS", 3);
-    return mode;
-}
-
+// H = 256 without a bf16 mask: gathered on both sides -> rows_wgrad_ls_kernel<0>, both operands in row order -> <1>, everything
+// else (mask bits, one index array, a second source in row order) -> rows_wgrad_dma_kernel.  Other widths and bf16 masks: the
+// register-staged rows_wgrad_kernel.
 template <int HI, int HO>
 int launch_wgrad(const bf16_t* A, const bf16_t* A2, int32_t na1, const int32_t* ia, const bf16_t* G, const bf16_t* G2,
                  int32_t ng1, const int32_t* ig, const Chunk* chunks, int64_t num_chunks, float* partial, int32_t colsum_of,
                  float* cs_partial, const bf16_t* maskA, bf16_t* A_out, const uint8_t* maskBits, float slope, hipStream_t st,
                  const int32_t* chunk_ptr = nullptr) {
-    if constexpr (HI == HO && (HI == 256 || HI == 128)) {
-        if (maskA == nullptr && A_out == nullptr && wgrad_dma_mode() >= (HI == 256 ? 1 : 2)) {
-            if constexpr (HI == 256) {
-                const bool dense_ls = ia == nullptr && ig == nullptr && A2 == nullptr && G2 == nullptr;
-                const int ls = wgrad_ls_mode();
-                const int ls_mode = (maskBits == nullptr && ia != nullptr && ig != nullptr) ? ((ls & 1) ? 0 : -1)
-                                    : (dense_ls ? (maskBits ? ((ls & 4) ? 2 : -1) : ((ls & 2) ? 1 : -1)) : -1);
-                if (ls_mode >= 0) {                                        // loaders and MFMA waves apart
-#define DN_WGRAD_LS(M)                                                                                                  \
-                    hipLaunchKernelGGL((rows_wgrad_ls_kernel<M>), dim3((unsigned)num_chunks), dim3(kLsThreads), 0, st, A, A2, na1, ia, \
-                                       G, G2, ng1, ig, chunks, partial, colsum_of, cs_partial, maskBits, slope,                     \
-                                       (M == 0 && wgrad_il_mode()) ? chunk_ptr : nullptr)
-                    if (ls_mode == 0) DN_WGRAD_LS(0);
-                    else if (ls_mode == 1) DN_WGRAD_LS(1);
-                    else DN_WGRAD_LS(2);
-#undef DN_WGRAD_LS
-                    DN_CHECK_LAUNCH();
-                    return DN_OK;
-                }
-                if (maskBits == nullptr && ia != nullptr && ig != nullptr && wgrad_ix_mode()) {   // gathered operands: index ring
-                    hipLaunchKernelGGL(rows_wgrad_ix_kernel, dim3((unsigned)num_chunks), dim3(kWgThreads), 0, st, A, A2,
-                                       na1, ia, G, G2, ng1, ig, chunks, partial, colsum_of, cs_partial);
-                    DN_CHECK_LAUNCH();
-                    return DN_OK;
-                }
-            }
+    if constexpr (HI == HO && HI == 256) {
+        if (maskA == nullptr && A_out == nullptr) {
             const bool dense = ia == nullptr && ig == nullptr && A2 == nullptr && G2 == nullptr;
+            const int ls_mode = (maskBits == nullptr && ia != nullptr && ig != nullptr) ? 0 : (dense ? (maskBits ? -1 : 1) : -1);
+            if (ls_mode >= 0) {                                            // loaders and MFMA waves apart
+#define DN_WGRAD_LS(M)                                                                                                  \
+                hipLaunchKernelGGL((rows_wgrad_ls_kernel<M>), dim3((unsigned)num_chunks), dim3(kLsThreads), 0, st, A, A2, na1, ia, \
+                                   G, G2, ng1, ig, chunks, partial, colsum_of, cs_partial, maskBits, slope,                     \
+                                   (M == 0 && wgrad_il_mode()) ? chunk_ptr : nullptr)
+                if (ls_mode == 0) DN_WGRAD_LS(0);
+                else DN_WGRAD_LS(1);
+#undef DN_WGRAD_LS
+                DN_CHECK_LAUNCH();
+                return DN_OK;
+            }
 #define DN_WGRAD_DMA(M, D)                                                                                            \
-            hipLaunchKernelGGL((rows_wgrad_dma_kernel<HI, M, D>), dim3((unsigned)num_chunks), dim3(kWgThreads), 0, st, A, A2, \
+            hipLaunchKernelGGL((rows_wgrad_dma_kernel<M, D>), dim3((unsigned)num_chunks), dim3(kWgThreads), 0, st, A, A2, \
                                na1, ia, G, G2, ng1, ig, chunks, partial, colsum_of, cs_partial, maskBits, slope)
             if (maskBits) {                                                // (mask bits come with ia == NULL: dn_rows_wgrad_bf16)
                 if (dense) DN_WGRAD_DMA(true, true);
                 else DN_WGRAD_DMA(true, false);
             } else {
-                if (dense) DN_WGRAD_DMA(false, true);
-                else DN_WGRAD_DMA(false, false);
+                DN_WGRAD_DMA(false, false);                                // (row order without mask bits went to ls_mode 1 above)
             }
 #undef DN_WGRAD_DMA
             DN_CHECK_LAUNCH();

@@ -257,6 +257,32 @@ def test_rows_transform_matches_reference(H, arith):
             torch.testing.assert_close(got[sel.to(DEV)].cpu().double(), ref_r, **tol)
 
 
+def test_rows_transform_identity_rows_over_two_sources_at_h256():
+    """dn_rows_transform_bf16 at H = 256 with idx == NULL and a second source: the one form that stays on the register-staged
+    rows_transform_kernel (the ring kernel tells the sources apart through the row index).  Relations of 33, 1 and 0 rows; reference
+    and tolerance of test_rows_transform_matches_reference."""
+    ops = _ops()
+    H = 256
+    rng = np.random.default_rng(10 + H)
+    sizes = [33, 1, 0]
+    rel_ptr = [0] + [int(v) for v in np.cumsum(sizes)]
+    R, P, N1 = len(sizes), rel_ptr[-1], 20
+    Xcat = torch.from_numpy(rng.standard_normal((P, H)).astype(np.float32)).to(torch.bfloat16)
+    Wn = torch.from_numpy((rng.standard_normal((R, H, H)) / np.sqrt(H)).astype(np.float32)).to(torch.bfloat16)
+    bias = torch.from_numpy(rng.standard_normal((R, H)).astype(np.float32)).to(torch.bfloat16)
+    tiles = ops.make_row_tiles(rel_ptr, DEV)
+    rel_of_row = torch.repeat_interleave(torch.arange(R), torch.tensor(sizes))
+    for use_bias, relu in [(False, False), (True, True)]:
+        got = ops.rows_transform(Xcat[:N1].contiguous().to(DEV), Wn.to(DEV), tiles, P, X2=Xcat[N1:].contiguous().to(DEV),
+                                 bias=bias.to(DEV) if use_bias else None, relu=relu)
+        ref = torch.einsum("pk,pnk->pn", Xcat.double(), Wn.double()[rel_of_row])
+        if use_bias:
+            ref = ref + bias.double()[rel_of_row]
+        if relu:
+            ref = ref.clamp(min=0)
+        torch.testing.assert_close(got.cpu().double(), ref, rtol=1e-2, atol=2e-2)
+
+
 @pytest.mark.parametrize("H", [64, 128, 256])
 @pytest.mark.parametrize("exact", [False, True])
 def test_fp32_transform_on_the_parameters_where_they_lie(H, exact):
@@ -663,6 +689,49 @@ def test_wgrad_ring_kernel_with_loader_waves_at_every_pipeline_length(rows):
         ref3 = am.t() @ g.double()
         assert float((got[0].cpu().double() - ref3).abs().max()) / max(1.0, float(ref3.abs().max())) < 1e-5
         assert float((cs[0].cpu().double() - am.sum(0)).abs().max()) < 1e-3 * max(1.0, float(am.sum(0).abs().max()))
+
+
+@pytest.mark.parametrize("case", ["mask_bits_gathered_g", "one_index_array", "bf16_mask"])
+def test_rows_wgrad_single_launch_kernels_beside_the_loader_waves(case):
+    """The forms of dn_rows_wgrad_bf16 at H = 256 that do NOT run on rows_wgrad_ls_kernel (test above): the A operand masked by bits
+    with a gathered, two-source G, and one index array only (rows_wgrad_dma_kernel<true, false> / <false, false>); a bf16 mask with
+    the masked operand written back (rows_wgrad_kernel).  Three relations of 33, 1 and 0 rows: a full 32-row tile, a one-row tail,
+    an empty relation.  Reference and bounds as in the test above."""
+    ops = _ops()
+    H, R, NS = 256, 3, 40
+    rng = np.random.default_rng(7)
+    bf = lambda a: torch.from_numpy(a.astype(np.float32)).to(torch.bfloat16)  # noqa: E731
+    d = lambda t: t.to(DEV)  # noqa: E731
+    rel_ptr = [0, 33, 34, 34]
+    P = rel_ptr[-1]
+    table = ops.make_row_chunks(rel_ptr, DEV, chunk_rows=2048)
+    rows, src = bf(rng.standard_normal((P, H))), bf(rng.standard_normal((NS, H)))     # an operand in row order, a gathered one
+    ix = torch.from_numpy(rng.integers(0, NS, size=P)).to(torch.int32)
+    slope = 0.25
+    if case == "mask_bits_gathered_g":
+        bits = torch.from_numpy(rng.integers(0, 256, size=(P, H // 8)).astype(np.uint8))
+        keep = ((bits.unsqueeze(-1) >> torch.arange(8, dtype=torch.uint8)) & 1).reshape(P, H).bool()
+        am = torch.where(keep, rows, (rows.float() * slope).to(torch.bfloat16)).double()    # (the scaled rows are rounded to bf16 in the tile)
+        gm = src[ix.long()].double()
+        got, cs = ops.rows_wgrad(d(rows), d(src[:25].contiguous()), table, R, idx_g=d(ix), G2=d(src[25:].contiguous()),
+                                 out_dtype=torch.float32, colsum_of=1, mask_a_bits=d(bits), slope=slope)
+    elif case == "one_index_array":
+        am, gm = src[ix.long()].double(), rows.double()
+        got, cs = ops.rows_wgrad(d(src[:25].contiguous()), d(rows), table, R, idx_a=d(ix), A2=d(src[25:].contiguous()),
+                                 out_dtype=torch.float32, colsum_of=1)
+    else:
+        mask = bf(rng.standard_normal((P, H)))
+        a_masked = torch.where(mask > 0, rows, (rows.float() * slope).to(torch.bfloat16))
+        am, gm = a_masked.double(), src[:P].double()
+        a_out = torch.zeros(P, H, dtype=torch.bfloat16, device=DEV)
+        got, cs = ops.rows_wgrad(d(rows), d(src[:P].contiguous()), table, R, out_dtype=torch.float32, colsum_of=1, mask_a=d(mask),
+                                 a_out=a_out, slope=slope)
+        assert torch.equal(a_out.cpu(), a_masked)
+    ref = torch.stack([am[a:b].t() @ gm[a:b] for a, b in zip(rel_ptr[:-1], rel_ptr[1:])])
+    cs_ref = torch.stack([am[a:b].sum(0) for a, b in zip(rel_ptr[:-1], rel_ptr[1:])])
+    assert float((got.cpu().double() - ref).abs().max()) / max(1.0, float(ref.abs().max())) < 1e-5
+    assert float((cs.cpu().double() - cs_ref).abs().max()) < 1e-3 * max(1.0, float(cs_ref.abs().max()))
+    assert not got[2].any() and not cs[2].any()                                        # the empty relation
 
 
 @pytest.mark.parametrize("H", [64, 128])

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the conv weight gradient alone (config 5 or a shard of it): python tools/wgrad_exp.py [--graphs 32768]
-(the tuning build's DN_WGRAD_IX=0 selects the scalar-index kernel)."""
+"""Timing of the conv weight gradient alone (config 5 or a shard of it): python tools/wgrad_exp.py [--graphs 32768]"""
 import argparse
 import os
 import sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the conv weight gradient (rows_wgrad_ix_kernel) costs when its gathers come from the caches: the same chunk table,
+"""What the conv weight gradient (rows_wgrad_ls_kernel<0>) costs when its gathers come from the caches: the same chunk table,
    the row indices folded into the first M rows of each operand (M rows x 512 B: 1 MB fits an XCD's L2, 16-64 MB the Infinity Cache).
    The distance between the real indices' time and the folded ones' bounds what any re-ordering of the rows could gain."""
 import os, sys
