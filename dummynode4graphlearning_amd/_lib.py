@@ -201,6 +201,13 @@ _SIGS = {
     "dn_seg_attn_bwd_kv_f32": (ctypes.c_int, [c_i64, c_i64, c_i64] + [c_i32] * 5 + [P] * 7 + [c_f32] + [P] * 5 + [P]),
     "dn_seg_window_pool_fwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_i32] + [P] * 7 + [P]),
     "dn_seg_window_pool_bwd_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_i32] + [P] * 6 + [P]),
+    "dn_diffpool_max_clusters": (c_i32, []),
+    "dn_diffpool_max_features": (c_i32, []),
+    "dn_diffpool_graph_rows": (c_i32, [c_i32]),
+    "dn_segment_gram_f32": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, P, c_i64] + [P] * 4 + [P]),
+    "dn_diffpool_softmax_fwd_f32": (ctypes.c_int, [c_i64, c_i32, P, P, P]),
+    "dn_diffpool_softmax_bwd_f32": (ctypes.c_int, [c_i64, c_i32] + [P] * 5 + [P]),
+    "dn_diffpool_assign_graphs_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32] + [P] * 10 + [P]),
 }
 
 _lib = None

@@ -24,12 +24,14 @@ class _IndexCache:
         self._rel = []  # [(etype tensor, version, num_rels, RelIndex)]
         self._lrp = {}  # {sequence length: ops.LrpIndex}
         self._hgt = []  # [(key tensor, version, tag, ops.HgtIndex / ops.TypeIndex)]
+        self._diffpool = None  # (ops.DiffPoolIndex, edge_index tensor, its version)
 
     def clear(self):
         self._edge_index = None
         self._rel = []
         self._lrp = {}
         self._hgt = []
+        self._diffpool = None
 
 
 class BatchedGraph:
@@ -302,6 +304,27 @@ def edge_index_of(data):
     if cache._edge_index is None or cache._edge_index.num_edges != data.edge_index.shape[1]:
         cache._edge_index = ops.EdgeIndex(data.edge_index[0], data.edge_index[1], data.x.shape[0], node_ptr=_node_ptr_or_none(data))
     return cache._edge_index
+
+
+def diffpool_index_of(data):
+    """Cached ops.DiffPoolIndex of a PyG-style batch: the graph boundaries on the host (its one read-back), the out-degrees and, on
+    the GPU, the batch's cached EdgeIndex, whose CSR by source the DiffPool level aggregates over."""
+    cache = getattr(data, "_cache", None)
+    if cache is None:
+        cache = _IndexCache()
+        try:
+            data._cache = cache
+        except Exception:
+            pass
+    hit = getattr(cache, "_diffpool", None)
+    ei = data.edge_index
+    if (hit is None or hit[1] is not ei or hit[2] != ei._version or hit[0].num_nodes != data.x.shape[0]
+            or hit[0].graph_ptr.device != data.x.device):
+        edge = edge_index_of(data) if data.x.is_cuda else None
+        ix = ops.DiffPoolIndex(ei[0], ei[1], graph_ptr_i32(data), data.x.shape[0], edge)
+        hit = (ix, ei, ei._version)                                   # (the tensor itself is kept: its id cannot be recycled)
+        cache._diffpool = hit
+    return hit[0]
 
 
 def row_index_of(data, etype, num_rels, self_loop, closing_hint=None):

@@ -892,7 +892,7 @@ class EdgeIndex:
         self._max_bwd = None
 
     @classmethod
-    def from_parts(cls, src, dst, num_nodes, node_ptr, in_ptr, in_perm, src_by_dst, out_ptr, out_perm, dst_by_src):
+    def from_parts(cls, src, dst, num_nodes, node_ptr, in_ptr, in_perm, src_by_dst, out_ptr, out_perm, dst_by_src, splits=None):
         """The index of a batch whose CSR by destination / CSC by source already exist (loader.PackedGraphs.assemble copies them out
         of the dataset's own, re-based): the six tensors are taken as they are -- int32, what __init__ would have built from
         (src, dst) -- and the hub split and the tile plan are derived from them exactly as there."""
@@ -908,8 +908,11 @@ class EdgeIndex:
         self.src, self.dst = src.to(I32).contiguous(), dst.to(I32).contiguous()
         self.in_ptr, self.in_perm, self.out_ptr, self.out_perm = in_ptr, in_perm, out_ptr, out_perm
         self.src_by_dst, self.dst_by_src = src_by_dst, dst_by_src
-        self.fwd = _SplitCSR(self.in_ptr, self.src_by_dst, self.num_nodes)
-        self.bwd = _SplitCSR(self.out_ptr, self.dst_by_src, self.num_nodes)
+        if splits is not None:                                      # (fwd, bwd) hub splits that exist for these very lists: no read-back
+            self.fwd, self.bwd = splits
+        else:
+            self.fwd = _SplitCSR(self.in_ptr, self.src_by_dst, self.num_nodes)
+            self.bwd = _SplitCSR(self.out_ptr, self.dst_by_src, self.num_nodes)
         self._max_bwd = None
         return self
 
@@ -4752,3 +4755,274 @@ def seg_window_pool(rows, ptr_, skip, mem_len, mode, max_len=None):
             and mem_len <= SEG_POOL_MAX_MEM and ptr_.numel() > 1):
         return _SegWindowPoolFn.apply(rows, ptr_, _u8_or_none(skip), mem_len, SEG_POOL_MODES[mode])
     return seg_window_pool_composed(rows, ptr_, skip, mem_len, mode, max_len)
+
+
+# ----------------------------------------------------------------------------------------------
+# DiffPool on ragged rows: per-graph products and the fused assignment (dn_diffpool.hip)
+# ----------------------------------------------------------------------------------------------
+DIFFPOOL_MAX_C = 256
+DIFFPOOL_MAX_F = 512
+
+# The default of diffpool_assign.  Measured on the config-2 and config-4 batches (docs/LAB_NOTES.md "GC: DiffPool"; 512 dummy-augmented
+# graphs, the reference's default dimensions, fused and composed alternated in one process): the assignment forward + backward 0.91
+# against 4.95 ms (config 2: 55 clusters) and 0.34 against 1.17 ms (config 4: 17 clusters), the model's training step 6.90 against
+# 10.57 ms and 6.54 against 7.03 ms, every fused round faster than every composed round -- the rule of the attention heads
+# (ATTN_FUSED_DEFAULT), so the fused kernels are the default.
+DIFFPOOL_FUSED_DEFAULT = True
+
+
+def diffpool_fused_enabled():
+    return diffpool_fused.override(DIFFPOOL_FUSED_DEFAULT)
+
+
+class diffpool_fused(_ThreadSwitch):
+    """Context manager: diffpool_assign calls made inside it (on this thread) run on dn_diffpool.hip (on=True) where
+    diffpool_fused_supported allows it, or on the composed path (on=False: the same ragged mathematics in torch ops)."""
+    _slot = "diffpool_fused"
+
+
+def diffpool_fused_supported(logits, z):
+    """The predicate of the fused assignment: fp32 rows on the GPU, 1 <= C <= 256 cluster columns, 1 <= F <= 512 feature columns."""
+    return (logits.is_cuda and z.is_cuda and logits.dtype == torch.float32 and z.dtype == torch.float32 and logits.dim() == 2
+            and z.dim() == 2 and 1 <= int(logits.shape[1]) <= DIFFPOOL_MAX_C and 1 <= int(z.shape[1]) <= DIFFPOOL_MAX_F)
+
+
+def diffpool_graph_rows(C):
+    """The most rows of a graph that one workgroup of dn_diffpool_assign_graphs_f32 takes whole at C cluster columns."""
+    return int(lib().dn_diffpool_graph_rows(int(C)))
+
+
+class DiffPoolIndex:
+    """What the DiffPool level on ragged rows needs of a batch, built once per batch (graph.diffpool_index_of caches it there):
+    the graph boundaries (int32 on the device AND as host integers -- ONE read-back of its own, which also verifies that every edge
+    names rows of the batch and stays inside its graph), the graph of every row, the edges, 1 / max(out-degree, 1), on the GPU the
+    batch's EdgeIndex and its transpose (the SAME six tensors and the same two hub splits with the roles of source and destination
+    exchanged, nothing rebuilt or read back: DenseSAGEConv aggregates over OUT-edges), the 64-row tile
+    table of the per-graph products' backward, and per cluster count the graphs one workgroup takes whole."""
+
+    def __init__(self, src, dst, graph_ptr, num_nodes, edge_index=None):
+        dev = graph_ptr.device
+        self.num_nodes, self.num_graphs = int(num_nodes), int(graph_ptr.numel() - 1)
+        self.src, self.dst = src.long(), dst.long()
+        p = graph_ptr.long()
+        sizes = p[1:] - p[:-1]
+        self.batch = torch.repeat_interleave(torch.arange(self.num_graphs, device=dev), sizes, output_size=self.num_nodes)
+        inside = in_range = torch.ones((), dtype=torch.bool, device=dev)
+        if self.src.numel() and self.num_nodes:
+            hi = self.num_nodes - 1                                               # (checked before anything is indexed by an edge id)
+            in_range = ((self.src >= 0) & (self.src <= hi) & (self.dst >= 0) & (self.dst <= hi)).all()
+            inside = (self.batch[self.src.clamp(0, hi)] == self.batch[self.dst.clamp(0, hi)]).all()
+        elif self.src.numel():
+            in_range = ~in_range
+        host = torch.cat([p, in_range.view(1).long(), inside.view(1).long()]).tolist()      # the one read-back
+        if not host[-2]:
+            raise _lib.DnHipError("DiffPool: an edge names a node outside the batch's %d rows" % self.num_nodes)
+        if not host[-1]:
+            raise _lib.DnHipError("DiffPool: an edge joins two graphs of the batch")
+        host = host[:-2]
+        if host[0] != 0 or host[-1] != self.num_nodes or any(b < a for a, b in zip(host[:-1], host[1:])):
+            raise _lib.DnHipError("DiffPool: the graph boundaries must rise from 0 to the number of rows")
+        self.ptr_host = host
+        self.sizes = [b - a for a, b in zip(self.ptr_host[:-1], self.ptr_host[1:])]
+        self.max_nodes = max(self.sizes) if self.sizes else 0
+        self.graph_ptr = graph_ptr.to(I32).contiguous()
+        self.out_deg = torch.bincount(self.src, minlength=self.num_nodes).clamp(min=1).view(-1, 1)
+        self._inv_out_deg = {}
+        self.edge = edge_index
+        self._edge_t = self._tiles = self._adj_sq = None
+        self._whole = {}
+
+    def inv_out_deg(self, dtype):
+        """1 / max(out-degree, 1) as an [N, 1] column of dtype."""
+        hit = self._inv_out_deg.get(dtype)
+        if hit is None:
+            hit = self._inv_out_deg[dtype] = 1.0 / self.out_deg.to(dtype)
+        return hit
+
+    @property
+    def padded_rows(self):
+        """B Nmax: the rows of the reference's padded batch."""
+        return self.num_graphs * self.max_nodes
+
+    @property
+    def edge_t(self):
+        """The batch's EdgeIndex read the other way round: its CSR by destination IS this batch's CSR by source."""
+        if self._edge_t is None:
+            e = self.edge
+            self._edge_t = EdgeIndex.from_parts(e.dst, e.src, e.num_nodes, None, e.out_ptr, e.out_perm, e.dst_by_src, e.in_ptr, e.in_perm,
+                                                e.src_by_dst, splits=(e.bwd, e.fwd))
+        return self._edge_t
+
+    @property
+    def tiles(self):
+        if self._tiles is None:
+            self._tiles = build_row_tables(self.graph_ptr, self.num_graphs, self.num_nodes, 64)
+        return self._tiles
+
+    def whole_graphs(self, C):
+        """(graphs taken whole [n] int32 or None, their largest row count, the other graphs [m] int32 or None) at C clusters."""
+        hit = self._whole.get(C)
+        if hit is None:
+            cap = diffpool_graph_rows(C)
+            small = [g for g, n in enumerate(self.sizes) if n <= cap]
+            big = [g for g, n in enumerate(self.sizes) if n > cap]
+            dev = self.graph_ptr.device
+            hit = (torch.tensor(small, dtype=I32, device=dev) if small else None, max([self.sizes[g] for g in small], default=0),
+                   torch.tensor(big, dtype=I32, device=dev) if big else None)
+            self._whole[C] = hit
+        return hit
+
+    def adj_sq_norm(self):
+        """||A||_F^2 of the dense adjacency: the squares of the multiplicities of the distinct (source, destination) pairs."""
+        if self._adj_sq is None:
+            _, cnt = torch.unique(self.src * self.num_nodes + self.dst, return_counts=True)
+            self._adj_sq = (cnt.double() ** 2).sum()
+        return self._adj_sq
+
+
+def _segment_gram_launch(L, R, graph_ptr, out, graphs=None):
+    B, (N, CL), CR = graph_ptr.numel() - 1, L.shape, R.shape[1]
+    launch_tagged("segment_gram", lambda: check(lib().dn_segment_gram_f32(
+        B, N, CL, CR, ptr(graphs), 0 if graphs is None else graphs.numel(), ptr(graph_ptr), ptr(L), ptr(R), ptr(out), stream_ptr()),
+        "dn_segment_gram_f32"))
+    return out
+
+
+class _SegmentGramFn(torch.autograd.Function):
+    """out [B, CL, CR] of dn_segment_gram_f32; backward: every row times its own graph's matrix, two dn_rows_gemm_f32 launches over the
+    64-row tiles of the graphs (as _TypedLinearFn with the graph as the type; the rows are already grouped)."""
+
+    @staticmethod
+    def forward(ctx, L, R, graph_ptr, tiles):
+        L, R = L.contiguous(), R.contiguous()
+        require_gpu(L, R, graph_ptr)
+        _i32(graph_ptr, "graph_ptr")
+        B = graph_ptr.numel() - 1
+        out = torch.empty((B, L.shape[1], R.shape[1]), dtype=torch.float32, device=L.device)
+        if L.shape[0]:
+            _segment_gram_launch(L, R, graph_ptr, out)
+        else:
+            out.zero_()
+        ctx.tiles = tiles
+        ctx.save_for_backward(L, R, graph_ptr)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L, R, graph_ptr = ctx.saved_tensors
+        dout = dout.contiguous()
+        tiles = ctx.tiles if ctx.tiles is not None else build_row_tables(graph_ptr, graph_ptr.numel() - 1, L.shape[0], 64)
+        dL = rows_gemm(R, dout, tiles, transpose_w=True) if ctx.needs_input_grad[0] else None        # R[p] dout[g]^T
+        dR = rows_gemm(L, dout, tiles) if ctx.needs_input_grad[1] else None                          # L[p] dout[g]
+        return dL, dR, None, None
+
+
+def _graph_of_rows(graph_ptr, num_rows):
+    p = graph_ptr.long()
+    return torch.repeat_interleave(torch.arange(p.numel() - 1, device=p.device), p[1:] - p[:-1], output_size=int(num_rows))
+
+
+def segment_gram_composed(L, R, graph_ptr, batch=None):
+    """The same per-graph products from torch ops on the ragged rows (any dtype, any device): the rows' outer products added into
+    their graph's matrix, a slab of rows at a time so that no temporary passes 2^24 elements."""
+    N, CL = L.shape
+    CR, B = R.shape[1], graph_ptr.numel() - 1
+    if batch is None:
+        batch = _graph_of_rows(graph_ptr, N)
+    out = L.new_zeros((B, CL, CR))
+    step = max(1, (1 << 24) // max(CL * CR, 1))
+    for a in range(0, N, step):
+        out.index_add_(0, batch[a:a + step], L[a:a + step].unsqueeze(2) * R[a:a + step].unsqueeze(1))
+    return out
+
+
+def segment_gram(L, R, graph_ptr, tiles=None):
+    """out [B, CL, CR]: out[g] = L[rows of graph g]^T R[rows of graph g], the rows of graph g = graph_ptr[g] .. graph_ptr[g + 1]
+    (graph_ptr [B + 1] int32).  fp32 on the GPU with CL <= 256 and CR <= 512: dn_segment_gram_f32 (exact-f32 MFMA, the same bits on
+    every run; autograd to L and R); anything else: segment_gram_composed.  tiles: the graphs' 64-row tile table when the caller has it."""
+    if L.dim() != 2 or R.dim() != 2 or L.shape[0] != R.shape[0] or graph_ptr.numel() < 2:
+        raise _lib.DnHipError("segment_gram: L [N, CL], R [N, CR] and graph_ptr [B + 1] with B >= 1 expected")
+    if (L.is_cuda and R.is_cuda and L.dtype == R.dtype == torch.float32 and 1 <= L.shape[1] <= DIFFPOOL_MAX_C
+            and 1 <= R.shape[1] <= DIFFPOOL_MAX_F):
+        return _SegmentGramFn.apply(L, R, graph_ptr, tiles)
+    return segment_gram_composed(L, R, graph_ptr)
+
+
+class _DiffPoolAssignFn(torch.autograd.Function):
+    """(X' [B, C, F], A' [B, C, C]) of the fused assignment.  Forward: the graphs whose S fits in LDS in ONE launch
+    (dn_diffpool_assign_graphs_f32); the others through a softmax launch, the gather over the CSR by source and dn_segment_gram_f32
+    restricted to them.  Saved: logits' softmax S and A S ([N, C] each).  Backward on the ragged rows:
+    dS = z dX'^T + (A S) dA'^T + A^T (S dA'), dz = S dX', dlogits = S (dS - rowsum(dS S)) -- four dn_rows_gemm_f32 launches over the graphs'
+    tiles, the gather over the CSR by destination and dn_diffpool_softmax_bwd_f32, which adds the three terms as it reads them."""
+
+    @staticmethod
+    def forward(ctx, logits, z, index):
+        logits, z = logits.contiguous(), z.contiguous()
+        require_gpu(logits, z, index.graph_ptr)
+        (N, C), F_ = logits.shape, z.shape[1]
+        B, e = index.num_graphs, index.edge
+        if z.shape[0] != N or index.num_nodes != N:
+            raise _lib.DnHipError("diffpool_assign: logits [N, C], z [N, F] and the batch's N rows expected")
+        dev = logits.device
+        S = torch.empty_like(logits)
+        X = torch.empty((B, C, F_), dtype=torch.float32, device=dev)
+        A = torch.empty((B, C, C), dtype=torch.float32, device=dev)
+        small, max_rows, big = index.whole_graphs(C)
+        if N == 0:
+            X.zero_(), A.zero_()
+        AS = torch.empty_like(logits) if big is None or not N else None
+        if big is not None and N:
+            # The softmax and the gather run over ALL rows although only the listed graphs' rows are used (the whole-graph launch below
+            # writes the others again, the same S bit for bit).  Restricting them needs a second CSR per (batch, C) over the listed
+            # graphs' rows -- exactly the graphs with a hub row, so with its own hub split -- to save two passes over [N, C] (config 2:
+            # 4.4 MB each, a few microseconds of the 0.9 ms); the products, which dominate, ARE restricted to the list.
+            launch_tagged("diffpool_softmax", lambda: check(lib().dn_diffpool_softmax_fwd_f32(N, C, ptr(logits), ptr(S), stream_ptr()),
+                                                           "dn_diffpool_softmax_fwd_f32"))
+            AS = e.bwd.segsum(S)                                                  # row i: the S rows of its out-edges' destinations
+            _segment_gram_launch(S, z, index.graph_ptr, X, big)
+            _segment_gram_launch(S, AS, index.graph_ptr, A, big)
+        if small is not None and N:
+            launch_tagged("diffpool_assign_graphs", lambda: check(lib().dn_diffpool_assign_graphs_f32(
+                B, N, e.num_edges, small.numel(), max_rows, C, F_, ptr(small), ptr(index.graph_ptr), ptr(e.out_ptr), ptr(e.dst_by_src),
+                ptr(logits), ptr(z), ptr(S), ptr(AS), ptr(X), ptr(A), stream_ptr()), "dn_diffpool_assign_graphs_f32"))
+        ctx.index = index
+        ctx.save_for_backward(z, S, AS)
+        return X, A
+
+    @staticmethod
+    def backward(ctx, dX, dA):
+        z, S, AS = ctx.saved_tensors
+        index = ctx.index
+        N, C = S.shape
+        dX, dA = dX.contiguous(), dA.contiguous()
+        if N == 0:
+            return torch.zeros_like(S), torch.zeros_like(z), None
+        tiles = index.tiles
+        dz = rows_gemm(S, dX, tiles) if ctx.needs_input_grad[1] else None
+        dlogits = None
+        if ctx.needs_input_grad[0]:
+            d0 = rows_gemm(z, dX, tiles, transpose_w=True)                         # z dX'^T
+            d1 = rows_gemm(AS, dA, tiles, transpose_w=True)                        # (A S) dA'^T
+            d2 = index.edge.fwd.segsum(rows_gemm(S, dA, tiles))                    # A^T (S dA'): row j gathers over its in-edges' sources
+            dlogits = torch.empty_like(S)
+            launch_tagged("diffpool_softmax_bwd", lambda: check(lib().dn_diffpool_softmax_bwd_f32(
+                N, C, ptr(S), ptr(d0), ptr(d1), ptr(d2), ptr(dlogits), stream_ptr()), "dn_diffpool_softmax_bwd_f32"))
+        return dlogits, dz, None
+
+
+def diffpool_assign_composed(logits, z, index):
+    """The same two products from torch ops on the ragged rows (any dtype, any device): softmax, index_add over the edges,
+    segment_gram_composed."""
+    S = torch.softmax(logits, dim=-1)
+    AS = torch.zeros_like(S).index_add(0, index.src, S.index_select(0, index.dst))
+    return segment_gram_composed(S, z, index.graph_ptr, index.batch), segment_gram_composed(S, AS, index.graph_ptr, index.batch)
+
+
+def diffpool_assign(logits, z, index):
+    """(X' [B, C, F], A' [B, C, C]) of dense_diff_pool on ragged rows: S = softmax(logits [N, C]) over the clusters, per graph
+    X' = S^T z (z [N, F]) and A' = S^T (A S), A the graph's adjacency with edge (src, dst) at A[src, dst] and duplicates summed.
+    index: the batch's DiffPoolIndex.  The fused kernels where diffpool_fused_enabled() and diffpool_fused_supported (fp32,
+    C <= 256, F <= 512), else the composed path.  Autograd to logits and z either way."""
+    if diffpool_fused_enabled() and diffpool_fused_supported(logits, z) and index.edge is not None:
+        return _DiffPoolAssignFn.apply(logits, z, index)
+    return diffpool_assign_composed(logits, z, index)

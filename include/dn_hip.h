@@ -1221,6 +1221,32 @@ int dn_seg_window_pool_fwd_f32(int64_t B, int64_t N, int32_t D, int32_t mem_len,
 int dn_seg_window_pool_bwd_f32(int64_t B, int64_t N, int32_t D, int32_t mem_len, int32_t mode, const int32_t* ptr, const uint8_t* skip,
                                const int32_t* span, const int32_t* arg, const float* dmem, float* drows, dn_stream_t stream);
 
+/* ---- DiffPool on ragged rows (dn_diffpool.hip) -------------------------------------------------------------------------------
+ * B graphs; graph g owns the rows graph_ptr[g] .. graph_ptr[g + 1] of every [N, .] operand (fp32).  No atomics: the same bits on
+ * every run.  C <= dn_diffpool_max_clusters() (256) cluster columns, F <= dn_diffpool_max_features() (512) feature columns.
+ *   dn_segment_gram_f32            out [B, CL, CR]: out[g] = L[rows_g]^T R[rows_g] (L [N, CL], CL <= 256; R [N, CR], CR <= 512) on the
+ *                                  exact-f32 MFMA, the rows of a graph in order; a graph without rows yields zeros.  graphs (may be
+ *                                  NULL, then num_list = 0): only the num_list graphs listed there are computed and written.
+ *   dn_diffpool_softmax_fwd_f32    S [N, C] = softmax of the rows of logits [N, C].
+ *   dn_diffpool_softmax_bwd_f32    dlogits = S (dS - rowsum(dS S)) with dS = d0 + d1 + d2 (d1, d2 may be NULL).
+ *   dn_diffpool_assign_graphs_f32  for the num_list graphs listed in `graphs` (each of at most max_rows <= dn_diffpool_graph_rows(C)
+ *                                  rows, so that S and A S fit in LDS), one workgroup per graph: S = softmax(logits) and
+ *                                  AS[i] = sum of S[dst_by_src[e]] over out_ptr[i] <= e < out_ptr[i + 1] (the CSR by source of the E
+ *                                  edges; an entry outside the graph's own rows is skipped) written to S, AS [N, C], and
+ *                                  X[g] = S^T z ([C, F], z [N, F]), A[g] = S^T AS ([C, C]) written to X [B, C, F], A [B, C, C].
+ *                                  Rows and graphs that are not listed are left untouched. */
+int32_t dn_diffpool_max_clusters(void);
+int32_t dn_diffpool_max_features(void);
+int32_t dn_diffpool_graph_rows(int32_t C);
+int dn_segment_gram_f32(int64_t B, int64_t N, int32_t CL, int32_t CR, const int32_t* graphs, int64_t num_list, const int32_t* graph_ptr,
+                        const float* L, const float* R, float* out, dn_stream_t stream);
+int dn_diffpool_softmax_fwd_f32(int64_t N, int32_t C, const float* logits, float* S, dn_stream_t stream);
+int dn_diffpool_softmax_bwd_f32(int64_t N, int32_t C, const float* S, const float* d0, const float* d1, const float* d2, float* dlogits,
+                                dn_stream_t stream);
+int dn_diffpool_assign_graphs_f32(int64_t B, int64_t N, int64_t E, int64_t num_list, int32_t max_rows, int32_t C, int32_t F,
+                                  const int32_t* graphs, const int32_t* graph_ptr, const int32_t* out_ptr, const int32_t* dst_by_src,
+                                  const float* logits, const float* z, float* S, float* AS, float* X, float* A, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
