@@ -208,6 +208,20 @@ _SIGS = {
     "dn_diffpool_softmax_fwd_f32": (ctypes.c_int, [c_i64, c_i32, P, P, P]),
     "dn_diffpool_softmax_bwd_f32": (ctypes.c_int, [c_i64, c_i32] + [P] * 5 + [P]),
     "dn_diffpool_assign_graphs_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32] + [P] * 10 + [P]),
+    "dn_hgpsl_topk_max_nodes": (c_i32, []),
+    "dn_hgpsl_wave_keys": (c_i32, []),
+    "dn_hgpsl_max_keys": (c_i32, []),
+    "dn_hgpsl_max_features": (c_i32, []),
+    "dn_hgpsl_att_slabs": (c_i32, []),
+    "dn_hgpsl_dinv_f32": (ctypes.c_int, [c_i64, c_i64] + [P] * 4 + [P]),
+    "dn_hgpsl_score_f32": (ctypes.c_int, [c_i64, c_i64, c_i32] + [P] * 7 + [P]),
+    "dn_hgpsl_topk_f32": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_i32] + [P] * 7 + [P]),
+    "dn_hgpsl_pq_f32": (ctypes.c_int, [c_i64, c_i32] + [P] * 4 + [P]),
+    "dn_hgpsl_structure_fwd_f32": (ctypes.c_int, [c_i64] * 6 + [c_i32, c_i32] + [P] * 12 + [c_f32, c_f32, P, P]),
+    "dn_hgpsl_structure_bwd_rows_f32": (ctypes.c_int, [c_i64] * 4 + [c_i32] + [P] * 6 + [c_f32] + [P] * 5 + [P]),
+    "dn_hgpsl_structure_bwd_cols_f32": (ctypes.c_int, [c_i64] * 4 + [P] * 6 + [P]),
+    "dn_hgpsl_structure_bwd_edges_f32": (ctypes.c_int, [c_i64] * 5 + [c_i32] + [P] * 9 + [c_f32, P, P]),
+    "dn_hgpsl_att_grad_f32": (ctypes.c_int, [c_i64, c_i32] + [P] * 5 + [P]),
 }
 
 _lib = None

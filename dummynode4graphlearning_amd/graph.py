@@ -25,6 +25,7 @@ class _IndexCache:
         self._lrp = {}  # {sequence length: ops.LrpIndex}
         self._hgt = []  # [(key tensor, version, tag, ops.HgtIndex / ops.TypeIndex)]
         self._diffpool = None  # (ops.DiffPoolIndex, edge_index tensor, its version)
+        self._hgpsl = None  # (ops.HgpslIndex, edge_index tensor, its version)
 
     def clear(self):
         self._edge_index = None
@@ -32,6 +33,7 @@ class _IndexCache:
         self._lrp = {}
         self._hgt = []
         self._diffpool = None
+        self._hgpsl = None
 
 
 class BatchedGraph:
@@ -324,6 +326,26 @@ def diffpool_index_of(data):
         ix = ops.DiffPoolIndex(ei[0], ei[1], graph_ptr_i32(data), data.x.shape[0], edge)
         hit = (ix, ei, ei._version)                                   # (the tensor itself is kept: its id cannot be recycled)
         cache._diffpool = hit
+    return hit[0]
+
+
+def hgpsl_index_of(data):
+    """Cached ops.HgpslIndex of a PyG-style batch: the graph boundaries on the host, the CSR by destination and by source, and the
+    checks of HGPSLPool's precondition (unique pairs, no edge between two graphs) -- one read-back per batch."""
+    cache = getattr(data, "_cache", None)
+    if cache is None:
+        cache = _IndexCache()
+        try:
+            data._cache = cache
+        except Exception:
+            pass
+    hit = getattr(cache, "_hgpsl", None)
+    ei = data.edge_index
+    if (hit is None or hit[1] is not ei or hit[2] != ei._version or hit[0].num_nodes != data.x.shape[0]
+            or hit[0].graph_ptr.device != data.x.device):
+        ix = ops.HgpslIndex(ei[0], ei[1], graph_ptr_i32(data), data.x.shape[0])
+        hit = (ix, ei, ei._version)
+        cache._hgpsl = hit
     return hit[0]
 
 

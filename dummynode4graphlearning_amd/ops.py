@@ -8,6 +8,7 @@ import os as _os
 import threading as _threading
 from typing import NamedTuple
 
+import numpy as _np
 import torch
 
 from . import _lib
@@ -5026,3 +5027,475 @@ def diffpool_assign(logits, z, index):
     if diffpool_fused_enabled() and diffpool_fused_supported(logits, z) and index.edge is not None:
         return _DiffPoolAssignFn.apply(logits, z, index)
     return diffpool_assign_composed(logits, z, index)
+
+
+# ----------------------------------------------------------------------------------------------
+# HGP-SL pooling on ragged per-graph blocks (dn_hgpsl.hip)
+# ----------------------------------------------------------------------------------------------
+HGPSL_MAX_H = 512
+HGPSL_WAVE_KEYS = 64
+HGPSL_MAX_KEYS = 1024
+HGPSL_TOPK_MAX_NODES = 4096
+HGPSL_ATT_SLABS = 64
+
+# The default of the HGP-SL ops, by the rule of ATTN_FUSED_DEFAULT / DIFFPOOL_FUSED_DEFAULT: on only if every fused round beats every
+# composed round.  Measured with tools/gc_hgpsl_bench.py on the config-2 and config-4 batches (docs/LAB_NOTES.md "GC: HGP-SL"; 512
+# dummy-augmented graphs, H = 128, ratio 0.8, fused and composed alternated in one process), softmax / sparsemax: score + top-k 0.21
+# against 0.48 / 0.46 ms (config 2) and 0.09 against 0.38 / 0.37 ms (config 4); structure forward + backward 0.26 / 0.26 against
+# 23.5 / 34.0 ms and 0.25 / 0.16 against 12.9 / 15.5 ms; the two-level stack's training step 6.74 / 4.91 against 63.0 / 62.8 ms and
+# 4.31 / 3.84 against 28.0 / 34.7 ms -- every fused round faster than every composed round in all twelve, so the kernels are the default.
+HGPSL_FUSED_DEFAULT = True
+
+
+def hgpsl_fused_enabled():
+    return hgpsl_fused.override(HGPSL_FUSED_DEFAULT)
+
+
+class hgpsl_fused(_ThreadSwitch):
+    """Context manager: hgpsl_score / hgpsl_topk / hgpsl_structure calls made inside it (on this thread) run on dn_hgpsl.hip (on=True)
+    where hgpsl_fused_supported allows it, or on the composed path (on=False: the same ragged mathematics in torch ops)."""
+    _slot = "hgpsl_fused"
+
+
+def hgpsl_fused_supported(x):
+    """The predicate of the fused HGP-SL kernels: fp32 rows on the GPU with 1 <= H <= 512 feature columns."""
+    return x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and 1 <= int(x.shape[1]) <= HGPSL_MAX_H
+
+
+def hgpsl_k(ratio, sizes):
+    """The kept nodes per graph, ceil(float32(ratio) float32(n)) in float32 exactly as torch computes (ratio * n.float()).ceil():
+    0.3 x 50 -> 16, not 15.  Host integers in, host integers out."""
+    if not sizes:
+        return []
+    k = (ratio * torch.tensor(sizes, dtype=torch.float32)).ceil().long().tolist()
+    return [min(int(a), int(n)) for a, n in zip(k, sizes)]
+
+
+def _dev_i32(values, device):
+    return torch.from_numpy(_np.asarray(values, dtype=_np.int32)).to(device)
+
+
+class HgpslPooled:
+    """The sizes of a batch after one HGP-SL pooling at `ratio`, all from the host copy of the graph sizes (no read-back): k per
+    graph, the pooled graph boundaries, the offsets of the ragged k x k blocks, and the class lists of the kernels."""
+
+    def __init__(self, index, ratio):
+        dev = index.graph_ptr.device
+        self.ratio = ratio
+        self.ks = hgpsl_k(ratio, index.sizes)
+        ks = _np.asarray(self.ks, dtype=_np.int64).reshape(-1)
+        ns = _np.asarray(index.sizes, dtype=_np.int64).reshape(-1)
+        self.ptr_host = [0] + _np.cumsum(ks).tolist()
+        self.blk_host = [0] + _np.cumsum(ks * ks).tolist()
+        self.num_rows, self.num_pairs, self.num_graphs = self.ptr_host[-1], self.blk_host[-1], len(self.ks)
+        self.graph_ptr = _dev_i32(self.ptr_host, dev)
+        self.blk_ptr = torch.from_numpy(_np.asarray(self.blk_host, dtype=_np.int64)).to(dev)
+        self.max_k = int(ks.max()) if ks.size else 0
+        # top-k classes by the graph's size, structure classes by its kept size
+        gid = _np.arange(ks.size)
+        self.topk_lists = []                                                  # (graphs int32 on the device, their largest size)
+        self.topk_big = gid[ns > HGPSL_TOPK_MAX_NODES].tolist()
+        self.rows_wave = self.rows_block = self.rows_fused = None
+        self.max_wave = self.max_block = 0
+        self.big = gid[ks > HGPSL_MAX_KEYS].tolist()
+        if dev.type == "cuda":
+            for m in ((ns >= 1) & (ns <= HGPSL_WAVE_KEYS), (ns > HGPSL_WAVE_KEYS) & (ns <= HGPSL_TOPK_MAX_NODES)):
+                if m.any():
+                    self.topk_lists.append((_dev_i32(gid[m], dev), int(ns[m].max())))
+            krow = _np.repeat(ks, ks)
+            rows = _np.arange(self.num_rows)
+            wave, block = krow <= HGPSL_WAVE_KEYS, (krow > HGPSL_WAVE_KEYS) & (krow <= HGPSL_MAX_KEYS)
+            if wave.any():
+                self.rows_wave, self.max_wave = _dev_i32(rows[wave], dev), int(krow[wave].max())
+            if block.any():
+                self.rows_block, self.max_block = _dev_i32(rows[block], dev), int(krow[block].max())
+            if wave.any() or block.any():
+                self.rows_fused = _dev_i32(rows[wave | block], dev)
+        self._groups = {}
+
+    def groups(self, graphs=None):
+        """[(k, graphs of that k as a host list)] for k >= 1, over all graphs or the listed ones."""
+        key = None if graphs is None else tuple(graphs)
+        hit = self._groups.get(key)
+        if hit is None:
+            by_k = {}
+            for g in (range(self.num_graphs) if graphs is None else graphs):
+                if self.ks[g] >= 1:
+                    by_k.setdefault(self.ks[g], []).append(g)
+            hit = self._groups[key] = sorted(by_k.items())
+        return hit
+
+    def group_chunks(self, graphs=None):
+        """[(k, first pooled rows [G], block offsets [G])] on the device: the groups cut into chunks of at most HGPSL_COMPOSED_CHUNK
+        elements of a dense [G, k, k] tensor.  Cached: a second call copies nothing to the device."""
+        key = ("chunks", None if graphs is None else tuple(graphs))
+        hit = self._groups.get(key)
+        if hit is None:
+            hit, dev = [], self.graph_ptr.device
+            for k, gs in self.groups(graphs):
+                step = max(1, HGPSL_COMPOSED_CHUNK // (k * k))
+                for s in range(0, len(gs), step):
+                    part = gs[s:s + step]
+                    hit.append((k, torch.tensor([self.ptr_host[g] for g in part], device=dev),
+                                torch.tensor([self.blk_host[g] for g in part], device=dev)))
+            self._groups[key] = hit
+        return hit
+
+
+class HgpslIndex:
+    """What HGPSLPool needs of a batch, built once per batch (graph.hgpsl_index_of caches it on the data object): the graph boundaries
+    (int32 on the device AND as host integers), the graph of every row, the edges, on the GPU their CSR by destination (col) and by
+    source (row), and the checks of the layer's precondition -- every edge names rows of the batch, no edge joins two graphs, no
+    (row, col) pair is repeated -- all in ONE read-back.  sizes: the host sizes when the caller already has them AND the edges are
+    the layer's own output (unique and inside their graphs by construction): then nothing is read back at all."""
+
+    def __init__(self, row, col, graph_ptr, num_nodes, sizes=None):
+        dev = graph_ptr.device
+        self.num_nodes, self.num_graphs = int(num_nodes), int(graph_ptr.numel() - 1)
+        self.row, self.col = row.long(), col.long()
+        self.num_edges = int(self.row.numel())
+        if sizes is None:
+            p = graph_ptr.long()
+            ok = torch.ones(3, dtype=torch.long, device=dev)
+            if self.num_edges and self.num_nodes:
+                hi = self.num_nodes - 1
+                in_range = ((self.row >= 0) & (self.row <= hi) & (self.col >= 0) & (self.col <= hi)).all()
+                r, c = self.row.clamp(0, hi), self.col.clamp(0, hi)
+                b = torch.searchsorted(p[1:].contiguous(), r, right=True)
+                inside = (b == torch.searchsorted(p[1:].contiguous(), c, right=True)).all()
+                key = torch.sort(r * self.num_nodes + c).values
+                unique = ~(key[1:] == key[:-1]).any()
+                ok = torch.stack([in_range, inside, unique]).long()
+            elif self.num_edges:
+                ok[0] = 0
+            host = torch.cat([p, ok]).tolist()                                    # the one read-back
+            flags, host = host[-3:], host[:-3]
+            if not flags[0]:
+                raise _lib.DnHipError("HGP-SL: an edge names a node outside the batch's %d rows" % self.num_nodes)
+            if not flags[1]:
+                raise _lib.DnHipError("HGP-SL: an edge joins two graphs of the batch")
+            if not flags[2]:
+                raise _lib.DnHipError("HGP-SL: a (row, col) pair is repeated (coalesce the edges first)")
+            if host[0] != 0 or host[-1] != self.num_nodes or any(b < a for a, b in zip(host[:-1], host[1:])):
+                raise _lib.DnHipError("HGP-SL: the graph boundaries must rise from 0 to the number of rows")
+            sizes = [b - a for a, b in zip(host[:-1], host[1:])]
+        self.sizes = [int(s) for s in sizes]
+        self.ptr_host = [0] + _np.cumsum(_np.asarray(self.sizes, dtype=_np.int64)).tolist() if self.sizes else [0]
+        self.graph_ptr = graph_ptr.to(I32).contiguous()
+        self.batch = torch.repeat_interleave(torch.arange(self.num_graphs, device=dev), graph_ptr.long()[1:] - graph_ptr.long()[:-1],
+                                             output_size=self.num_nodes)
+        self._pooled = {}
+        self.row32 = self.col32 = self.in_ptr = self.in_perm = self.src_by_dst = self.out_ptr = self.out_perm = self.dst_by_src = None
+        if dev.type == "cuda" and self.num_nodes:
+            self.row32, self.col32 = self.row.to(I32).contiguous(), self.col.to(I32).contiguous()
+            if self.num_edges:
+                self.in_ptr, self.in_perm = csr_build(self.col32, self.num_nodes)
+                self.out_ptr, self.out_perm = csr_build(self.row32, self.num_nodes)
+            else:
+                self.in_ptr = self.out_ptr = torch.zeros(self.num_nodes + 1, dtype=I32, device=dev)
+                self.in_perm = self.out_perm = torch.zeros(0, dtype=I32, device=dev)
+            self.src_by_dst = gather_rows_i32(self.row32, self.in_perm)
+            self.dst_by_src = gather_rows_i32(self.col32, self.out_perm)
+
+    @classmethod
+    def from_batch(cls, edge_index, batch, num_nodes):
+        """From PyG's (edge_index, batch) when no graph boundaries are at hand: the number of graphs costs a read-back of its own."""
+        if batch is None:
+            batch = edge_index.new_zeros(num_nodes)
+        ng = int(batch.max().item()) + 1 if batch.numel() else 1
+        cnt = torch.bincount(batch, minlength=ng)
+        p = torch.cat([cnt.new_zeros(1), torch.cumsum(cnt, 0)])
+        return cls(edge_index[0], edge_index[1], p, num_nodes)
+
+    def pooled(self, ratio):
+        """The HgpslPooled of this batch at `ratio` (cached): the next level's sizes on the host, no read-back."""
+        hit = self._pooled.get(ratio)
+        if hit is None:
+            hit = self._pooled[ratio] = HgpslPooled(self, ratio)
+        return hit
+
+
+def _hgpsl_weights(index, edge_attr, like):
+    if edge_attr is None:
+        return None
+    if edge_attr.dim() != 1 or edge_attr.numel() != index.num_edges:
+        raise _lib.DnHipError("HGP-SL: edge_attr must hold one weight per edge ([%d], got %s)" % (index.num_edges, tuple(edge_attr.shape)))
+    return edge_attr.to(like.dtype)
+
+
+def hgpsl_score_composed(x, index, edge_attr=None):
+    """The node information score from torch ops (any dtype, any device)."""
+    x = x.detach()
+    w = _hgpsl_weights(index, edge_attr, x)
+    w = x.new_ones(index.num_edges) if w is None else w.detach()
+    deg = x.new_zeros(index.num_nodes).index_add_(0, index.row, w)
+    dinv = deg.pow(-0.5)
+    dinv[dinv == float("inf")] = 0
+    coef = dinv[index.row] * w * dinv[index.col]
+    agg = torch.zeros_like(x).index_add_(0, index.col, coef.view(-1, 1) * x.index_select(0, index.row))
+    return (x - agg).abs().sum(dim=1)
+
+
+def hgpsl_score(x, index, edge_attr=None):
+    """score [N] = || ((I - D^-1/2 A D^-1/2) x)_i ||_1 with the degree taken over the edges' rows (NodeInformationScore of the
+    reference); no gradient.  Fused: one small launch for D^-1/2 and ONE launch for the weighted gather fused with the row sum."""
+    if x.dim() != 2 or x.shape[0] != index.num_nodes:
+        raise _lib.DnHipError("hgpsl_score: x [N, H] with the batch's N = %d rows expected" % index.num_nodes)
+    if not (hgpsl_fused_enabled() and hgpsl_fused_supported(x)) or index.num_nodes == 0:
+        return hgpsl_score_composed(x, index, edge_attr)
+    x = x.detach().contiguous()
+    w = _hgpsl_weights(index, edge_attr, x)
+    w = None if w is None else w.detach().contiguous()
+    require_gpu(x, w, index.in_ptr)
+    N, E, H = index.num_nodes, index.num_edges, x.shape[1]
+    dinv = torch.empty(N, dtype=torch.float32, device=x.device)
+    score = torch.empty(N, dtype=torch.float32, device=x.device)
+    launch_tagged("hgpsl_dinv", lambda: check(lib().dn_hgpsl_dinv_f32(N, E, ptr(index.out_ptr), ptr(index.out_perm), ptr(w), ptr(dinv),
+                                                                     stream_ptr()), "dn_hgpsl_dinv_f32"))
+    launch_tagged("hgpsl_score", lambda: check(lib().dn_hgpsl_score_f32(N, E, H, ptr(index.in_ptr), ptr(index.in_perm), ptr(index.src_by_dst),
+                                                                       ptr(w), ptr(dinv), ptr(x), ptr(score), stream_ptr()),
+                                               "dn_hgpsl_score_f32"))
+    return score
+
+
+class HgpslSelection:
+    """The kept nodes of one pooling: perm [N'] (each graph's kept nodes by descending score, ties to the lower node), batch [N'] and
+    inv [N] (the pooled row of a kept node, -1 of a dropped one); int64 for indexing, int32 for the kernels."""
+
+    def __init__(self, perm, batch, inv):
+        self.perm32, self.batch32, self.inv32 = perm, batch, inv
+        self.perm, self.batch, self.inv = perm.long(), batch.long(), inv.long()
+
+
+def _hgpsl_topk_torch(score, index, pooled, graphs, perm, batch, inv):
+    """The selection of the listed graphs (None: all) from two stable sorts, written into perm / batch / inv (int32)."""
+    dev = score.device
+    if graphs is None:
+        nodes, gb = torch.arange(index.num_nodes, device=dev), index.batch
+    else:
+        ranges = [_np.arange(index.ptr_host[g], index.ptr_host[g + 1]) for g in graphs]
+        nodes = torch.from_numpy(_np.concatenate(ranges) if ranges else _np.zeros(0, dtype=_np.int64)).to(dev)
+        gb = index.batch.index_select(0, nodes)
+    if nodes.numel() == 0:
+        return
+    o1 = torch.sort(score.index_select(0, nodes), descending=True, stable=True).indices       # ties keep the lower node first
+    o2 = torch.sort(gb.index_select(0, o1), stable=True).indices
+    order = nodes.index_select(0, o1.index_select(0, o2))                                      # by graph, then by descending score
+    g_of = index.batch.index_select(0, order)
+    gptr, pptr = index.graph_ptr.long(), pooled.graph_ptr.long()
+    # `order` lists the chosen graphs' nodes graph by graph: the rank of an entry is its distance from its graph's first entry
+    sizes = gptr[1:] - gptr[:-1]
+    if graphs is not None:
+        chosen = torch.as_tensor(list(graphs), device=dev)
+        sizes = torch.zeros_like(sizes).index_copy_(0, chosen, sizes.index_select(0, chosen))
+    start = torch.cumsum(sizes, 0) - sizes
+    rank = torch.arange(order.numel(), device=dev) - start.index_select(0, g_of)
+    keep = rank < (pptr[1:] - pptr[:-1]).index_select(0, g_of)
+    slot = pptr.index_select(0, g_of) + rank
+    inv.index_copy_(0, order, torch.where(keep, slot, torch.full_like(slot, -1)).to(I32))
+    tgt = torch.where(keep, slot, torch.full_like(slot, pooled.num_rows))                      # dropped entries land in a spare slot
+    perm_x, batch_x = torch.cat([perm, perm.new_zeros(1)]), torch.cat([batch, batch.new_zeros(1)])
+    perm_x.scatter_(0, tgt, order.to(I32))
+    batch_x.scatter_(0, tgt, g_of.to(I32))
+    perm.copy_(perm_x[:-1])
+    batch.copy_(batch_x[:-1])
+
+
+def hgpsl_topk(score, index, pooled):
+    """HgpslSelection of the pooling: per graph the k = pooled.ks[g] nodes of the highest scores.  Fused: the u64 keys
+    (~score bits << 32) | local index sorted per graph by a wavefront (<= 64 nodes) or a workgroup in LDS (<= 4096 nodes); larger
+    graphs, and everything on the composed path, by two stable torch sorts.  No read-back."""
+    dev = score.device
+    N, Np = index.num_nodes, pooled.num_rows
+    perm = torch.zeros(Np, dtype=I32, device=dev)
+    batch = torch.zeros(Np, dtype=I32, device=dev)
+    inv = torch.full((N,), -1, dtype=I32, device=dev)
+    if N == 0 or Np == 0:
+        return HgpslSelection(perm, batch, inv)
+    fused = hgpsl_fused_enabled() and score.is_cuda and score.dtype == torch.float32
+    if not fused:
+        _hgpsl_topk_torch(score, index, pooled, None, perm, batch, inv)
+        return HgpslSelection(perm, batch, inv)
+    score = score.contiguous()
+    require_gpu(score, index.graph_ptr, pooled.graph_ptr)
+    for graphs, max_nodes in pooled.topk_lists:
+        launch_tagged("hgpsl_topk", lambda: check(lib().dn_hgpsl_topk_f32(
+            index.num_graphs, N, Np, graphs.numel(), max_nodes, ptr(graphs), ptr(index.graph_ptr), ptr(pooled.graph_ptr), ptr(score),
+            ptr(perm), ptr(batch), ptr(inv), stream_ptr()), "dn_hgpsl_topk_f32"))
+    if pooled.topk_big:
+        _hgpsl_topk_torch(score, index, pooled, pooled.topk_big, perm, batch, inv)
+    return HgpslSelection(perm, batch, inv)
+
+
+def hgpsl_filter(index, sel, edge_attr=None):
+    """filter_adj: the edges with both ends kept, renumbered through perm, their order kept (one sync for the count)."""
+    r, c = sel.inv.index_select(0, index.row), sel.inv.index_select(0, index.col)
+    mask = (r >= 0) & (c >= 0)
+    return torch.stack([r[mask], c[mask]]), (None if edge_attr is None else edge_attr[mask])
+
+
+def _sparsemax_rows(z):
+    """sparsemax over the last dimension (Martins & Astudillo 2016, as sparse_softmax.py computes it)."""
+    z = z - z.max(dim=-1, keepdim=True).values
+    srt = torch.sort(z, dim=-1, descending=True).values
+    cs = srt.cumsum(dim=-1) - 1.0
+    rho = torch.arange(1, z.shape[-1] + 1, dtype=z.dtype, device=z.device)
+    kk = (rho * srt > cs).sum(dim=-1, keepdim=True).clamp(min=1)
+    tau = cs.gather(-1, kk - 1) / kk.to(z.dtype)
+    return torch.clamp(z - tau, min=0)
+
+
+def _softmax_rows(z):
+    """PyG's grouped softmax on a dense group: the maximum subtracted, 1e-16 added to the sum."""
+    e = (z - z.max(dim=-1, keepdim=True).values).exp()
+    return e / (e.sum(dim=-1, keepdim=True) + 1e-16)
+
+
+def _hgpsl_adjacency(index, pooled, sel, w, dtype):
+    """lamb-free A as ragged blocks [T + 1] (a spare slot takes the edges with a dropped end): the pairs are unique, so every slot but
+    the spare one has at most one writer."""
+    r, c = sel.inv.index_select(0, index.row), sel.inv.index_select(0, index.col)
+    valid = (r >= 0) & (c >= 0)
+    rr, cc = r.clamp(min=0), c.clamp(min=0)
+    g = sel.batch.index_select(0, rr) if pooled.num_rows else rr
+    c0, kg = pooled.graph_ptr.long().index_select(0, g), (pooled.graph_ptr.long()[1:] - pooled.graph_ptr.long()[:-1]).index_select(0, g)
+    pos = pooled.blk_ptr.index_select(0, g) + (rr - c0) * kg + (cc - c0)
+    pos = torch.where(valid, pos, torch.full_like(pos, pooled.num_pairs))
+    vals = valid.to(dtype) if w is None else w * valid.to(dtype)
+    return torch.zeros(pooled.num_pairs + 1, dtype=dtype, device=r.device).index_put((pos,), vals, accumulate=True)
+
+
+HGPSL_COMPOSED_CHUNK = 1 << 22               # elements of one dense [G, k, k] group of the composed path
+
+
+def hgpsl_structure_composed(xp, att, edge_attr, index, pooled, sel, sparse=False, lamb=1.0, negative_slop=0.2, graphs=None,
+                             positions=False):
+    """The ragged blocks [sum k^2] from torch ops (any dtype, any device; autograd to xp, att and edge_attr): the graphs grouped by
+    k, each group a dense [G, k, k] chunk -- no Python loop over single graphs, nothing of size N'^2.  graphs: only those (host
+    list); the other blocks stay zero.  positions=True: returns (flat positions, values) of the computed blocks instead."""
+    H = xp.shape[1]
+    a = att.reshape(-1).to(xp.dtype)
+    p, q = xp @ a[:H], xp @ a[H:]
+    dev = xp.device
+    w = _hgpsl_weights(index, edge_attr, xp)
+    A = _hgpsl_adjacency(index, pooled, sel, w, xp.dtype) if index.num_edges and pooled.num_rows else None
+    pos_all, val_all = [], []
+    for k, c0, b0 in pooled.group_chunks(graphs):
+        rows = (c0.view(-1, 1) + torch.arange(k, device=dev)).reshape(-1)
+        P, Q = p.index_select(0, rows).view(-1, k, 1), q.index_select(0, rows).view(-1, 1, k)
+        z = torch.nn.functional.leaky_relu(P + Q, negative_slop)
+        bpos = (b0.view(-1, 1) + torch.arange(k * k, device=dev)).reshape(-1)
+        if A is not None:
+            z = z + A.index_select(0, bpos).view(-1, k, k) * lamb
+        o = _sparsemax_rows(z) if sparse else _softmax_rows(z)
+        pos_all.append(bpos)
+        val_all.append(o.reshape(-1))
+    if not pos_all:
+        pos_cat, val_cat = torch.zeros(0, dtype=torch.long, device=dev), xp.new_zeros(0)
+    else:
+        pos_cat, val_cat = torch.cat(pos_all), torch.cat(val_all)
+    if positions:
+        return pos_cat, val_cat
+    return xp.new_zeros(pooled.num_pairs).index_copy(0, pos_cat, val_cat)
+
+
+class _HgpslStructureFn(torch.autograd.Function):
+    """The ragged blocks of the graphs with k <= 1024 (the others' stay zero).  Forward: p, q (one launch), then one launch per
+    class (a wavefront or a workgroup per row).  Saved: xp, att, p, q and the blocks themselves -- the output decides the Jacobian
+    (softmax: o (g - <o, g>); sparsemax: g - mean over o > 0) and the sign of p_i + q_j the leaky slope, so no logit is kept or
+    recomputed.  Backward: the row pass (dl, dp, the row terms), the column pass (dq), the edge pass (lamb dz at each induced edge)
+    and the fixed-order reduction for att."""
+
+    @staticmethod
+    def forward(ctx, xp, att, w, index, pooled, sel, sparse, lamb, slope):
+        ctx.att_shape = att.shape
+        xp, att = xp.contiguous(), att.contiguous().view(-1)
+        w = None if w is None else w.contiguous()
+        require_gpu(xp, att, w, sel.perm32, sel.inv32)
+        Np, H = xp.shape
+        N, E, B, T = index.num_nodes, index.num_edges, index.num_graphs, pooled.num_pairs
+        dev = xp.device
+        mode = SEG_SCORES["sparsemax" if sparse else "softmax"]
+        p = torch.empty(Np, dtype=torch.float32, device=dev)
+        q = torch.empty(Np, dtype=torch.float32, device=dev)
+        launch_tagged("hgpsl_pq", lambda: check(lib().dn_hgpsl_pq_f32(Np, H, ptr(xp), ptr(att), ptr(p), ptr(q), stream_ptr()), "dn_hgpsl_pq_f32"))
+        blocks = torch.zeros(T, dtype=torch.float32, device=dev) if pooled.big else torch.empty(T, dtype=torch.float32, device=dev)
+        for rows, max_keys in ((pooled.rows_wave, pooled.max_wave), (pooled.rows_block, pooled.max_block)):
+            if rows is None:
+                continue
+            launch_tagged("hgpsl_structure_fwd", lambda: check(lib().dn_hgpsl_structure_fwd_f32(
+                B, N, E, Np, T, rows.numel(), max_keys, mode, ptr(rows), ptr(pooled.graph_ptr), ptr(pooled.blk_ptr), ptr(sel.batch32),
+                ptr(sel.perm32), ptr(sel.inv32), ptr(index.out_ptr), ptr(index.out_perm), ptr(index.dst_by_src), ptr(w), ptr(p), ptr(q),
+                lamb, slope, ptr(blocks), stream_ptr()), "dn_hgpsl_structure_fwd_f32"))
+        ctx.args = (index, pooled, sel, mode, lamb, slope, w is not None)
+        ctx.save_for_backward(xp, att, p, q, blocks)
+        return blocks
+
+    @staticmethod
+    def backward(ctx, dblocks):
+        xp, att, p, q, blocks = ctx.saved_tensors
+        index, pooled, sel, mode, lamb, slope, has_w = ctx.args
+        Np, H = xp.shape
+        N, E, B, T = index.num_nodes, index.num_edges, index.num_graphs, pooled.num_pairs
+        dev = xp.device
+        dblocks = dblocks.contiguous()
+        rows = pooled.rows_fused
+        dp = torch.zeros(Np, dtype=torch.float32, device=dev)
+        dq = torch.zeros(Np, dtype=torch.float32, device=dev)
+        rterm = torch.zeros(Np, dtype=torch.float32, device=dev)
+        dl = torch.empty(T, dtype=torch.float32, device=dev)
+        dxp = datt = dw = None
+        if rows is not None:
+            launch_tagged("hgpsl_structure_bwd_rows", lambda: check(lib().dn_hgpsl_structure_bwd_rows_f32(
+                B, Np, T, rows.numel(), mode, ptr(rows), ptr(pooled.graph_ptr), ptr(pooled.blk_ptr), ptr(sel.batch32), ptr(p), ptr(q), slope,
+                ptr(blocks), ptr(dblocks), ptr(dl), ptr(dp), ptr(rterm), stream_ptr()), "dn_hgpsl_structure_bwd_rows_f32"))
+            launch_tagged("hgpsl_structure_bwd_cols", lambda: check(lib().dn_hgpsl_structure_bwd_cols_f32(
+                B, Np, T, rows.numel(), ptr(rows), ptr(pooled.graph_ptr), ptr(pooled.blk_ptr), ptr(sel.batch32), ptr(dl), ptr(dq),
+                stream_ptr()), "dn_hgpsl_structure_bwd_cols_f32"))
+        if has_w and ctx.needs_input_grad[2]:
+            dw = torch.zeros(E, dtype=torch.float32, device=dev)
+            if E and rows is not None:
+                launch_tagged("hgpsl_structure_bwd_edges", lambda: check(lib().dn_hgpsl_structure_bwd_edges_f32(
+                    B, N, E, Np, T, mode, ptr(index.row32), ptr(index.col32), ptr(sel.inv32), ptr(pooled.graph_ptr), ptr(pooled.blk_ptr),
+                    ptr(sel.batch32), ptr(blocks), ptr(dblocks), ptr(rterm), lamb, ptr(dw), stream_ptr()),
+                    "dn_hgpsl_structure_bwd_edges_f32"))
+        if ctx.needs_input_grad[0]:
+            dxp = torch.addcmul(dp.view(-1, 1) * att[:H].view(1, -1), dq.view(-1, 1), att[H:].view(1, -1))
+        if ctx.needs_input_grad[1]:
+            datt = torch.empty(2 * H, dtype=torch.float32, device=dev)
+            ws = torch.empty(HGPSL_ATT_SLABS * 2 * H, dtype=torch.float32, device=dev)
+            launch_tagged("hgpsl_att_grad", lambda: check(lib().dn_hgpsl_att_grad_f32(Np, H, ptr(xp), ptr(dp), ptr(dq), ptr(ws), ptr(datt),
+                                                                                     stream_ptr()), "dn_hgpsl_att_grad_f32"))
+            datt = datt.view(ctx.att_shape)
+        return dxp, datt, dw, None, None, None, None, None, None
+
+
+def hgpsl_structure(xp, att, edge_attr, index, pooled, sel, sparse=False, lamb=1.0, negative_slop=0.2):
+    """The learned structure of the pooled batch as ragged blocks [sum k_g^2]: graph g's k_g x k_g block, row-major, at
+    pooled.blk_host[g]; row i holds softmax_j or sparsemax_j of leaky_relu(<xp_i, att_l> + <xp_j, att_r>) + lamb A_ij over the kept
+    nodes j of the row's graph.  xp [N', H] = x[perm], att [1, 2 H] (or [2 H]), edge_attr [E] or None (ones).  Autograd to xp, att and
+    edge_attr.  The fused kernels where hgpsl_fused_enabled() and hgpsl_fused_supported (fp32, GPU, H <= 512); graphs with more than
+    1024 kept nodes take hgpsl_structure_composed on their own, within the same call."""
+    if xp.dim() != 2 or xp.shape[0] != pooled.num_rows or att.numel() != 2 * xp.shape[1]:
+        raise _lib.DnHipError("hgpsl_structure: xp [N', H] with the pooled batch's N' = %d rows and att [2 H] expected" % pooled.num_rows)
+    if not (hgpsl_fused_enabled() and hgpsl_fused_supported(xp) and att.dtype == torch.float32) or pooled.num_rows == 0:
+        return hgpsl_structure_composed(xp, att, edge_attr, index, pooled, sel, sparse, lamb, negative_slop)
+    w = _hgpsl_weights(index, edge_attr, xp)
+    blocks = _HgpslStructureFn.apply(xp, att, w, index, pooled, sel, bool(sparse), float(lamb), float(negative_slop))
+    if pooled.big:
+        pos, val = hgpsl_structure_composed(xp, att, edge_attr, index, pooled, sel, sparse, lamb, negative_slop, graphs=pooled.big,
+                                            positions=True)
+        blocks = blocks.index_copy(0, pos, val)
+    return blocks
+
+
+def hgpsl_compact(blocks, pooled):
+    """dense_to_sparse on the ragged blocks: (edge_index [2, M] over the pooled rows, weights [M]) of the entries that are not
+    exactly zero, in row-major order.  The data-dependent count costs the layer's one unavoidable sync."""
+    nz = blocks.detach().nonzero().view(-1)
+    g = torch.searchsorted(pooled.blk_ptr[1:].contiguous(), nz, right=True)
+    pptr = pooled.graph_ptr.long()
+    c0, k = pptr.index_select(0, g), (pptr[1:] - pptr[:-1]).index_select(0, g)
+    off = nz - pooled.blk_ptr.index_select(0, g)
+    r = torch.div(off, k.clamp(min=1), rounding_mode="floor")
+    return torch.stack([c0 + r, c0 + off - r * k]), blocks.index_select(0, nz)

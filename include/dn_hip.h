@@ -1247,6 +1247,60 @@ int dn_diffpool_assign_graphs_f32(int64_t B, int64_t N, int64_t E, int64_t num_l
                                   const int32_t* graphs, const int32_t* graph_ptr, const int32_t* out_ptr, const int32_t* dst_by_src,
                                   const float* logits, const float* z, float* S, float* AS, float* X, float* A, dn_stream_t stream);
 
+/* ---- HGP-SL pooling on ragged per-graph blocks (dn_hgpsl.hip) ----------------------------------------------------------------
+ * B graphs; graph g owns the rows graph_ptr[g] .. graph_ptr[g + 1] of the batch and the kept rows pooled_ptr[g] .. pooled_ptr[g + 1]
+ * (k_g of them, computed on the host) of the pooled batch of Np rows.  The per-pair storage is the ragged blocks: graph g's
+ * k_g x k_g block, row-major, at blk_ptr[g] (int64) of a float array of T = sum k_g^2 entries.  Edges (row, col) with their CSR by
+ * row (out_ptr, out_perm, dst_by_src) and by col (in_ptr, in_perm, src_by_dst); w [E] in edge order, NULL = ones.  fp32, no
+ * atomics: the same bits on every run.  H <= dn_hgpsl_max_features() (512).
+ *   dn_hgpsl_dinv_f32    dinv [N] = deg^-1/2 (0 where deg == 0), deg[v] = sum of w over the edges with row == v.
+ *   dn_hgpsl_score_f32   score[i] = sum_f |x[i, f] - sum_{e: col = i} dinv[row_e] w_e dinv[i] x[row_e, f]|.
+ *   dn_hgpsl_topk_f32    for the num_list graphs in `graphs` (each of at most max_nodes <= dn_hgpsl_topk_max_nodes() (4096) rows):
+ *                        perm [Np] = the k_g rows of the highest scores, descending, ties to the lower row; pooled_batch [Np] = g;
+ *                        inv [N] = the pooled row of a kept row, -1 of a dropped one.  Scores must be >= 0 and not NaN.
+ *   dn_hgpsl_pq_f32      p[i] = <xp[i], att[:H]>, q[i] = <xp[i], att[H:]>  (xp [Np, H], att [2 H]).
+ *   dn_hgpsl_structure_fwd_f32  for the num_rows pooled rows in `rows` (each of a graph with k_g <= max_keys <= dn_hgpsl_max_keys()
+ *                        (1024); up to dn_hgpsl_wave_keys() (64): a wavefront per row, else a workgroup): the block row
+ *                        softmax_j or sparsemax_j of leaky_relu(p_i + q_j, slope) + lamb A_ij, A_ij = the weight of the edge
+ *                        (perm[i], perm[j]) or 0; score: DN_SCORE_SOFTMAX (max subtracted, 1e-16 added to the sum) or
+ *                        DN_SCORE_SPARSEMAX.  Rows that are not listed are left untouched.
+ *   dn_hgpsl_structure_bwd_rows_f32   dl [T] = the gradient of leaky_relu's argument, dp [Np] = its row sums, rterm [Np] = the row
+ *                        term of the Jacobian (softmax: <o, g>; sparsemax: the mean of g over the support), for the listed rows.
+ *   dn_hgpsl_structure_bwd_cols_f32   dq [Np] = the column sums of dl over the graph's rows in order, for the listed rows.
+ *   dn_hgpsl_structure_bwd_edges_f32  dw [E] = lamb dz at the edge's pair; 0 for an edge with a dropped end or of a graph over
+ *                        dn_hgpsl_max_keys().
+ *   dn_hgpsl_att_grad_f32  datt [2 H] = [sum_i dp_i xp_i, sum_j dq_j xp_j]; ws: dn_hgpsl_att_slabs() x 2 H floats. */
+int32_t dn_hgpsl_topk_max_nodes(void);
+int32_t dn_hgpsl_wave_keys(void);
+int32_t dn_hgpsl_max_keys(void);
+int32_t dn_hgpsl_max_features(void);
+int32_t dn_hgpsl_att_slabs(void);
+int dn_hgpsl_dinv_f32(int64_t N, int64_t E, const int32_t* out_ptr, const int32_t* out_perm, const float* w, float* dinv,
+                      dn_stream_t stream);
+int dn_hgpsl_score_f32(int64_t N, int64_t E, int32_t H, const int32_t* in_ptr, const int32_t* in_perm, const int32_t* src_by_dst,
+                       const float* w, const float* dinv, const float* x, float* score, dn_stream_t stream);
+int dn_hgpsl_topk_f32(int64_t B, int64_t N, int64_t Np, int64_t num_list, int32_t max_nodes, const int32_t* graphs,
+                      const int32_t* graph_ptr, const int32_t* pooled_ptr, const float* score, int32_t* perm, int32_t* pooled_batch,
+                      int32_t* inv, dn_stream_t stream);
+int dn_hgpsl_pq_f32(int64_t Np, int32_t H, const float* xp, const float* att, float* p, float* q, dn_stream_t stream);
+int dn_hgpsl_structure_fwd_f32(int64_t B, int64_t N, int64_t E, int64_t Np, int64_t T, int64_t num_rows, int32_t max_keys, int32_t score,
+                               const int32_t* rows, const int32_t* pooled_ptr, const int64_t* blk_ptr, const int32_t* pooled_batch,
+                               const int32_t* perm, const int32_t* inv, const int32_t* out_ptr, const int32_t* out_perm,
+                               const int32_t* dst_by_src, const float* w, const float* p, const float* q, float lamb, float slope,
+                               float* blocks, dn_stream_t stream);
+int dn_hgpsl_structure_bwd_rows_f32(int64_t B, int64_t Np, int64_t T, int64_t num_rows, int32_t score, const int32_t* rows,
+                                    const int32_t* pooled_ptr, const int64_t* blk_ptr, const int32_t* pooled_batch, const float* p,
+                                    const float* q, float slope, const float* blocks, const float* dblocks, float* dl, float* dp,
+                                    float* rterm, dn_stream_t stream);
+int dn_hgpsl_structure_bwd_cols_f32(int64_t B, int64_t Np, int64_t T, int64_t num_rows, const int32_t* rows, const int32_t* pooled_ptr,
+                                    const int64_t* blk_ptr, const int32_t* pooled_batch, const float* dl, float* dq, dn_stream_t stream);
+int dn_hgpsl_structure_bwd_edges_f32(int64_t B, int64_t N, int64_t E, int64_t Np, int64_t T, int32_t score, const int32_t* src,
+                                     const int32_t* dst, const int32_t* inv, const int32_t* pooled_ptr, const int64_t* blk_ptr,
+                                     const int32_t* pooled_batch, const float* blocks, const float* dblocks, const float* rterm, float lamb,
+                                     float* dw, dn_stream_t stream);
+int dn_hgpsl_att_grad_f32(int64_t Np, int32_t H, const float* xp, const float* dp, const float* dq, float* ws, float* datt,
+                          dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
