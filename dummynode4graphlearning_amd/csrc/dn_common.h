@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "dn_hip.h"
+
 #define DN_OK 0
 #define DN_ERR_ARG (-1)
 #define DN_ERR_HIP (-2)
@@ -35,6 +37,27 @@ void dn_set_error(const char* fmt, ...);
 
 static inline int64_t dn_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t dn_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// lo doubled until it reaches x (lo a power of two: the padded length of a bitonic sort)
+static inline int dn_pow2_at_least(int lo, int x) {
+    int n = lo;
+    while (n < x) n <<= 1;
+    return n;
+}
+
+// A launch with more than 64 KB of dynamic LDS needs the kernel's limit raised first.
+template <typename K>
+static inline int dn_allow_lds(K kernel, size_t bytes) {
+    if (bytes > 64 * 1024)
+        DN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return DN_OK;
+}
+
+// the score functions of the ragged-row kernels
+static inline int dn_check_score(const char* what, int32_t score) {
+    DN_REQUIRE(score == DN_SCORE_SPARSEMAX || score == DN_SCORE_SOFTMAX, "%s: bad score function %d", what, score);
+    return DN_OK;
+}
 
 // Experiment knobs.  The shipped library has NO environment access of its own: every knob is its compile-time default (the
 // measured best).  A tuning build (-DDN_TUNING_ENV: `python -m dummynode4graphlearning_amd.csrc.build --tuning`, used by

@@ -15,6 +15,7 @@
 // bits on every run.  fp32 only.
 #include "dn_common.h"
 #include "dn_hip.h"
+#include "dn_rows.h"
 
 namespace {
 
@@ -106,17 +107,6 @@ __global__ __launch_bounds__(kBlock) void segment_gram_kernel(int64_t B, int64_t
 }
 
 // ---------------------------------------------------------------------------------------------- row softmax: one wavefront per row
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 constexpr int kPerLane = kMaxC / 64;     // columns lane, lane + 64, ... of a row
 
 // s[i] = softmax(x)[lane + 64 i]  (0 past C)
@@ -128,14 +118,14 @@ __device__ __forceinline__ void dp_softmax_row(const float* __restrict__ x, int 
         s[i] = c < C ? x[c] : -INFINITY;
         mx = fmaxf(mx, s[i]);
     }
-    mx = wave_max(mx);
+    mx = dn_wave_max(mx);
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < kPerLane; ++i) {
         s[i] = lane + 64 * i < C ? expf(s[i] - mx) : 0.f;
         sum += s[i];
     }
-    sum = wave_sum(sum);
+    sum = dn_wave_sum(sum);
     const float inv = 1.f / sum;
 #pragma unroll
     for (int i = 0; i < kPerLane; ++i) s[i] *= inv;
@@ -172,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void softmax_bwd_kernel(int64_t N, int C, c
         }
         dot += s[i] * d[i];
     }
-    dot = wave_sum(dot);
+    dot = dn_wave_sum(dot);
 #pragma unroll
     for (int i = 0; i < kPerLane; ++i)
         if (lane + 64 * i < C) dx[row * C + lane + 64 * i] = s[i] * (d[i] - dot);
@@ -221,9 +211,8 @@ __global__ __launch_bounds__(kBlock) void assign_graphs_kernel(int64_t B, int64_
 #pragma unroll
         for (int i = 0; i < kPadLane; ++i) a[i] = 0.f;
         if (r < n) {
-            int64_t e0 = optr[beg + r], e1 = optr[beg + r + 1];
-            e0 = e0 < 0 ? 0 : e0;
-            e1 = e1 > E ? E : e1;
+            int64_t e0, e1;
+            dn_csr_range(optr, beg + r, E, e0, e1);
             for (int64_t e = e0; e < e1; ++e) {
                 const int64_t d = (int64_t)onbr[e] - beg;
                 if (d < 0 || d >= n) continue;                            // (an edge that leaves its graph: the host refuses such a batch)
@@ -331,9 +320,7 @@ int dn_diffpool_assign_graphs_f32(int64_t B, int64_t N, int64_t E, int64_t num_l
                "dn_diffpool_assign_graphs: NULL pointer");
     const int np_max = (max_rows + 15) / 16 * 16;
     const size_t lds = ((size_t)2 * np_max * dp_stride(C) + kKT * kRS) * sizeof(float);
-    if (lds > 64 * 1024)
-        DN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assign_graphs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
+    if (int rc = dn_allow_lds(assign_graphs_kernel, lds)) return rc;
     hipLaunchKernelGGL(assign_graphs_kernel, dim3((unsigned)num_list), dim3(kBlock), lds, (hipStream_t)stream, B, N, E, C, F, np_max, graphs,
                        graph_ptr, out_ptr, dst_by_src, logits, z, S, AS, X, A);
     DN_CHECK_LAUNCH();

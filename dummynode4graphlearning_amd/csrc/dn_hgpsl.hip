@@ -25,6 +25,7 @@
 
 #include "dn_common.h"
 #include "dn_hip.h"
+#include "dn_rows.h"
 #include "dn_wl_common.h"
 
 namespace {
@@ -36,24 +37,6 @@ constexpr int kWaveKeys = 64;
 constexpr int kBlockKeys = 1024;
 constexpr int kTopkMaxNodes = 4096;          // 32 KB of u64 keys in LDS
 
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// 64 values, one per lane, sorted descending over the lanes (as dn_seg_attn.hip)
-__device__ __forceinline__ float wave_sort_desc(float v, int lane) {
-    for (int k = 2; k <= 64; k <<= 1)
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            const float u = __shfl_xor(v, j, 64);
-            const bool keep_max = ((lane & k) == 0) == ((lane & j) == 0);
-            v = keep_max ? fmaxf(v, u) : fminf(v, u);
-        }
-    return v;
-}
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // ---------------------------------------------------------------------------------------------- dinv and the score
@@ -62,18 +45,10 @@ __global__ __launch_bounds__(kBlock) void dinv_kernel(int64_t N, int64_t E, cons
                                                       float* __restrict__ dinv) {
     const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (v >= N) return;
-    int64_t e0 = out_ptr[v], e1 = out_ptr[v + 1];
-    e0 = e0 < 0 ? 0 : e0;
-    e1 = e1 > E ? E : e1;
+    int64_t e0, e1;
+    dn_csr_range(out_ptr, v, E, e0, e1);
     float deg = 0.f;
-    for (int64_t e = e0; e < e1; ++e) {
-        float we = 1.f;
-        if (w) {
-            const int32_t id = out_perm[e];
-            we = (id >= 0 && id < E) ? w[id] : 0.f;
-        }
-        deg += we;
-    }
+    for (int64_t e = e0; e < e1; ++e) deg += dn_edge_weight(w, out_perm, e, E);
     dinv[v] = deg > 0.f ? 1.f / sqrtf(deg) : 0.f;
 }
 
@@ -84,9 +59,8 @@ __global__ __launch_bounds__(kBlock) void score_kernel(int64_t N, int64_t E, int
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
     if (i >= N) return;
-    int64_t e0 = in_ptr[i], e1 = in_ptr[i + 1];
-    e0 = e0 < 0 ? 0 : e0;
-    e1 = e1 > E ? E : e1;
+    int64_t e0, e1;
+    dn_csr_range(in_ptr, i, E, e0, e1);
     const float di = dinv[i];
     float total = 0.f;
     for (int f0 = 0; f0 < H; f0 += 64) {
@@ -95,17 +69,12 @@ __global__ __launch_bounds__(kBlock) void score_kernel(int64_t N, int64_t E, int
         for (int64_t e = e0; e < e1; ++e) {                                 // (wave-uniform)
             const int64_t s = src_by_dst[e];
             if (s < 0 || s >= N) continue;
-            float we = 1.f;
-            if (w) {
-                const int32_t id = in_perm[e];
-                we = (id >= 0 && id < E) ? w[id] : 0.f;
-            }
-            const float coef = dinv[s] * we * di;
+            const float coef = dinv[s] * dn_edge_weight(w, in_perm, e, E) * di;
             if (f < H) agg += coef * x[s * H + f];
         }
         if (f < H) total += fabsf(x[i * H + f] - agg);
     }
-    total = wave_sum(total);
+    total = dn_wave_sum(total);
     if (lane == 0) score[i] = total;
 }
 
@@ -180,8 +149,8 @@ __global__ __launch_bounds__(kBlock) void pq_kernel(int64_t Np, int H, const flo
         a = fmaf(v, att[f], a);
         b = fmaf(v, att[H + f], b);
     }
-    a = wave_sum(a);
-    b = wave_sum(b);
+    a = dn_wave_sum(a);
+    b = dn_wave_sum(b);
     if (lane == 0) { p[i] = a; q[i] = b; }
 }
 
@@ -218,39 +187,24 @@ __global__ __launch_bounds__(kBlock) void structure_fwd_wave_kernel(int64_t B, i
     float z = live ? leaky(p[r.i] + q[r.c0 + lane], slope) : -INFINITY;
     const int64_t node = perm[r.i];
     if (node >= 0 && node < N) {
-        int64_t e0 = out_ptr[node], e1 = out_ptr[node + 1];
-        e0 = e0 < 0 ? 0 : e0;
-        e1 = e1 > E ? E : e1;
+        int64_t e0, e1;
+        dn_csr_range(out_ptr, node, E, e0, e1);
         for (int64_t e = e0; e < e1; ++e) {                                 // every lane reads the same edge; the pairs are unique
             const int64_t c = dst_by_src[e];
             if (c < 0 || c >= N) continue;
             if ((int64_t)inv[c] != r.c0 + lane || !live) continue;
-            float we = 1.f;
-            if (w) {
-                const int32_t id = out_perm[e];
-                we = (id >= 0 && id < E) ? w[id] : 0.f;
-            }
-            z += we * lamb;
+            z += dn_edge_weight(w, out_perm, e, E) * lamb;
         }
     }
-    const float mx = wave_max(z);
+    const float mx = dn_wave_max(z);
     float o;
     if (kSoft) {
         const float ex = live ? expf(z - mx) : 0.f;
-        const float s = wave_sum(ex);
+        const float s = dn_wave_sum(ex);
         o = ex / (s + 1e-16f);
     } else {
         const float zc = z - mx;                                           // (-inf on the lanes past the row)
-        const float s = wave_sort_desc(zc, lane);
-        const bool has = s > -INFINITY;
-        float cs = has ? s : 0.f;
-        for (int d = 1; d < 64; d <<= 1) {
-            const float u = __shfl_up(cs, d, 64);
-            if (lane >= d) cs += u;
-        }
-        const bool in = has && (float)(lane + 1) * s > cs - 1.f;
-        const int kk = __popcll(__ballot(in));                             // (>= 1: the first lane holds 0 and 0 > -1)
-        const float tau = (__shfl(cs, kk > 0 ? kk - 1 : 0, 64) - 1.f) / (float)(kk > 0 ? kk : 1);
+        const float tau = dn_sparsemax_tau_wave(zc, lane, DnSupportOps());
         o = live ? fmaxf(zc - tau, 0.f) : 0.f;
     }
     if (live) blocks[r.at + lane] = o;
@@ -278,72 +232,35 @@ __global__ __launch_bounds__(kBlock) void structure_fwd_block_kernel(int64_t B, 
     __syncthreads();
     const int64_t node = perm[r.i];
     if (node >= 0 && node < N) {
-        int64_t e0 = out_ptr[node], e1 = out_ptr[node + 1];
-        e0 = e0 < 0 ? 0 : e0;
-        e1 = e1 > E ? E : e1;
+        int64_t e0, e1;
+        dn_csr_range(out_ptr, node, E, e0, e1);
         for (int64_t e = e0 + tid; e < e1; e += kBlock) {                   // the pairs are unique: every slot has one writer
             const int64_t c = dst_by_src[e];
             if (c < 0 || c >= N) continue;
             const int64_t j = (int64_t)inv[c] - r.c0;
             if (j < 0 || j >= r.k) continue;
-            float we = 1.f;
-            if (w) {
-                const int32_t id = out_perm[e];
-                we = (id >= 0 && id < E) ? w[id] : 0.f;
-            }
-            zs[j] += we * lamb;
+            zs[j] += dn_edge_weight(w, out_perm, e, E) * lamb;
         }
     }
     __syncthreads();
     if (!kSoft) {
         for (int j = tid; j < n2; j += kBlock) srt[j] = zs[j];
         __syncthreads();
-        for (int k2 = 2; k2 <= n2; k2 <<= 1)
-            for (int j2 = k2 >> 1; j2 >= 1; j2 >>= 1) {
-                for (int i = tid; i < (n2 >> 1); i += kBlock) {
-                    const int a = ((i & ~(j2 - 1)) << 1) | (i & (j2 - 1));
-                    const float x = srt[a], y = srt[a | j2];
-                    const bool desc = (a & k2) == 0;
-                    if ((x < y) == desc) { srt[a] = y; srt[a | j2] = x; }
-                }
-                __syncthreads();
-            }
+        dn_sort_desc_lists<kBlock>(srt, 1, n2, tid);
     }
     if (tid < 64) {                                                       // the first wavefront: the maximum and the sum, or the threshold
         if (kSoft) {
             float m = -INFINITY;
             for (int j = lane; j < n2; j += 64) m = fmaxf(m, zs[j]);
-            m = wave_max(m);
+            m = dn_wave_max(m);
             float s = 0.f;
             for (int j = lane; j < r.k; j += 64) s += expf(zs[j] - m);
-            s = wave_sum(s);
+            s = dn_wave_sum(s);
             if (lane == 0) { st[0] = m; st[1] = s; }
         } else {
-            const float m = srt[0];
-            const int C = n2 >> 6;                                        // (n2 >= 128 in this class)
-            float ls = 0.f;
-            for (int c = 0; c < C; ++c) {
-                const float x = srt[lane * C + c];
-                if (x > -INFINITY) ls += x - m;
-            }
-            float cs = ls;                                                // inclusive scan of the lanes' chunk sums
-            for (int d = 1; d < 64; d <<= 1) {
-                const float u = __shfl_up(cs, d, 64);
-                if (lane >= d) cs += u;
-            }
-            cs -= ls;
-            float cnt = 0.f, ssum = 0.f;
-            for (int c = 0; c < C; ++c) {
-                const float x = srt[lane * C + c];
-                if (x > -INFINITY) {
-                    const float zc = x - m;
-                    cs += zc;
-                    if ((float)(lane * C + c + 1) * zc > cs - 1.f) { cnt += 1.f; ssum += zc; }
-                }
-            }
-            cnt = wave_sum(cnt);
-            ssum = wave_sum(ssum);
-            if (lane == 0) { st[0] = m; st[1] = cnt > 0.f ? (ssum - 1.f) / cnt : 0.f; }
+            float m, tau;
+            dn_sparsemax_tau_sorted(srt, n2, lane, DnSupportOps(), m, tau);
+            if (lane == 0) { st[0] = m; st[1] = tau; }
         }
     }
     __syncthreads();
@@ -372,19 +289,19 @@ __global__ __launch_bounds__(kBlock) void structure_bwd_rows_kernel(int64_t B, i
         if (kSoft) s1 = fmaf(o, g, s1);
         else if (o > 0.f) { s1 += g; cnt += 1.f; }
     }
-    s1 = wave_sum(s1);
-    cnt = wave_sum(cnt);
+    s1 = dn_wave_sum(s1);
+    cnt = dn_wave_sum(cnt);
     const float term = kSoft ? s1 : (cnt > 0.f ? s1 / cnt : 0.f);
     const float pi = p[r.i];
     float acc = 0.f;
     for (int j = lane; j < r.k; j += 64) {
         const float o = blocks[r.at + j], g = dblocks[r.at + j];
-        const float dz = kSoft ? o * (g - term) : (o > 0.f ? g - term : 0.f);
+        const float dz = dn_score_dz(kSoft, o, g - term);
         const float d = pi + q[r.c0 + j] > 0.f ? dz : dz * slope;
         dl[r.at + j] = d;
         acc += d;
     }
-    acc = wave_sum(acc);
+    acc = dn_wave_sum(acc);
     if (lane == 0) { dp[r.i] = acc; rterm[r.i] = term; }
 }
 
@@ -419,7 +336,7 @@ __global__ __launch_bounds__(kBlock) void structure_bwd_edges_kernel(int64_t B, 
             const RowAt r = row_at(B, Np, T, i, pptr, bptr, pbatch, kBlockKeys);
             if (r.ok && j >= r.c0 && j < r.c0 + r.k) {
                 const float o = blocks[r.at + (j - r.c0)], g = dblocks[r.at + (j - r.c0)];
-                out = lamb * (kSoft ? o * (g - rterm[i]) : (o > 0.f ? g - rterm[i] : 0.f));
+                out = lamb * dn_score_dz(kSoft, o, g - rterm[i]);
             }
         }
     }
@@ -481,17 +398,6 @@ int check_h(const char* what, int32_t H) {
     return DN_OK;
 }
 
-int check_score(const char* what, int32_t score) {
-    DN_REQUIRE(score == DN_SCORE_SPARSEMAX || score == DN_SCORE_SOFTMAX, "%s: bad score function %d", what, score);
-    return DN_OK;
-}
-
-int pow2_at_least(int lo, int x) {
-    int n = lo;
-    while (n < x) n <<= 1;
-    return n;
-}
-
 }  // namespace
 
 extern "C" {
@@ -534,7 +440,7 @@ int dn_hgpsl_topk_f32(int64_t B, int64_t N, int64_t Np, int64_t num_list, int32_
         hipLaunchKernelGGL(topk_wave_kernel, dim3((unsigned)dn_cdiv(num_list, kWaves)), dim3(kBlock), 0, (hipStream_t)stream, B, N, Np, num_list,
                            graphs, graph_ptr, pooled_ptr, score, perm, pooled_batch, inv);
     } else {
-        const int n2 = pow2_at_least(128, max_nodes);
+        const int n2 = dn_pow2_at_least(128, max_nodes);
         hipLaunchKernelGGL(topk_block_kernel, dim3((unsigned)num_list), dim3(kBlock), (size_t)n2 * sizeof(u64), (hipStream_t)stream, B, N, Np, n2,
                            graphs, graph_ptr, pooled_ptr, score, perm, pooled_batch, inv);
     }
@@ -562,7 +468,7 @@ int dn_hgpsl_structure_fwd_f32(int64_t B, int64_t N, int64_t E, int64_t Np, int6
                (long long)Np);
     DN_REQUIRE(max_keys >= 1 && max_keys <= kBlockKeys, "dn_hgpsl_structure_fwd: key count over the class limit: 1 <= max_keys <= %d (got %d)",
                kBlockKeys, max_keys);
-    if (int rc = check_score("dn_hgpsl_structure_fwd", score)) return rc;
+    if (int rc = dn_check_score("dn_hgpsl_structure_fwd", score)) return rc;
     DN_REQUIRE(rows && pooled_ptr && blk_ptr && pooled_batch && perm && inv && out_ptr && p && q && blocks && (dst_by_src || E == 0) &&
                    (!w || out_perm || E == 0),
                "dn_hgpsl_structure_fwd: NULL pointer");
@@ -573,7 +479,7 @@ int dn_hgpsl_structure_fwd_f32(int64_t B, int64_t N, int64_t E, int64_t Np, int6
         hipLaunchKernelGGL(kern, dim3((unsigned)dn_cdiv(num_rows, kWaves)), dim3(kBlock), 0, st, B, N, E, Np, T, num_rows, rows, pooled_ptr,
                            blk_ptr, pooled_batch, perm, inv, out_ptr, out_perm, dst_by_src, w, p, q, lamb, slope, blocks);
     } else {
-        const int n2 = pow2_at_least(128, max_keys);
+        const int n2 = dn_pow2_at_least(128, max_keys);
         auto kern = soft ? structure_fwd_block_kernel<true> : structure_fwd_block_kernel<false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)num_rows), dim3(kBlock), ((size_t)2 * n2 + 2) * sizeof(float), st, B, N, E, Np, T, n2, rows,
                            pooled_ptr, blk_ptr, pooled_batch, perm, inv, out_ptr, out_perm, dst_by_src, w, p, q, lamb, slope, blocks);
@@ -589,7 +495,7 @@ int dn_hgpsl_structure_bwd_rows_f32(int64_t B, int64_t Np, int64_t T, int64_t nu
     if (int rc = check_pooled("dn_hgpsl_structure_bwd_rows", B, Np, T)) return rc;
     DN_REQUIRE(num_rows >= 1 && num_rows <= Np, "dn_hgpsl_structure_bwd_rows: bad list (%lld rows listed of %lld)", (long long)num_rows,
                (long long)Np);
-    if (int rc = check_score("dn_hgpsl_structure_bwd_rows", score)) return rc;
+    if (int rc = dn_check_score("dn_hgpsl_structure_bwd_rows", score)) return rc;
     DN_REQUIRE(rows && pooled_ptr && blk_ptr && pooled_batch && p && q && blocks && dblocks && dl && dp && rterm,
                "dn_hgpsl_structure_bwd_rows: NULL pointer");
     auto kern = score == DN_SCORE_SOFTMAX ? structure_bwd_rows_kernel<true> : structure_bwd_rows_kernel<false>;
@@ -618,7 +524,7 @@ int dn_hgpsl_structure_bwd_edges_f32(int64_t B, int64_t N, int64_t E, int64_t Np
     if (int rc = check_batch("dn_hgpsl_structure_bwd_edges", N, E)) return rc;
     DN_REQUIRE(E >= 1, "dn_hgpsl_structure_bwd_edges: bad sizes (E = %lld; must be positive)", (long long)E);
     if (int rc = check_pooled("dn_hgpsl_structure_bwd_edges", B, Np, T)) return rc;
-    if (int rc = check_score("dn_hgpsl_structure_bwd_edges", score)) return rc;
+    if (int rc = dn_check_score("dn_hgpsl_structure_bwd_edges", score)) return rc;
     DN_REQUIRE(src && dst && inv && pooled_ptr && blk_ptr && pooled_batch && blocks && dblocks && rterm && dw,
                "dn_hgpsl_structure_bwd_edges: NULL pointer");
     auto kern = score == DN_SCORE_SOFTMAX ? structure_bwd_edges_kernel<true> : structure_bwd_edges_kernel<false>;

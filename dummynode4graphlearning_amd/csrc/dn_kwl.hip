@@ -352,8 +352,7 @@ int dn_kwl_global_u64(int64_t num_graphs, int64_t num_tuples, int64_t num_list, 
     const size_t cells = (size_t)lds_nodes * lds_nodes;
     const size_t lds = cells * (sizeof(u64) + 1) + (size_t)lds_nodes * 4 * sizeof(uint32_t);
     const int threads = lds_nodes <= 16 ? 64 : lds_nodes == 32 ? 256 : lds_nodes == 64 ? 512 : 1024;
-    if (lds > 65536)
-        DN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kwl_global_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = dn_allow_lds(kwl_global_kernel, lds)) return rc;
     hipLaunchKernelGGL(kwl_global_kernel, dim3((unsigned)num_list), dim3(threads), lds, (hipStream_t)stream, graphs, lds_nodes, (int)malkin,
                        node_ptr, tuple_ptr, ptr, nbr, reinterpret_cast<const u64*>(colors_in), reinterpret_cast<u64*>(colors_out),
                        reinterpret_cast<u64*>(work), num_tuples);

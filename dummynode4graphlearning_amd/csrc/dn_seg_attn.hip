@@ -33,6 +33,7 @@
 
 #include "dn_common.h"
 #include "dn_hip.h"
+#include "dn_rows.h"
 
 namespace {
 
@@ -47,17 +48,6 @@ constexpr int kBlockQTile = 8;
 constexpr int kBwdQTile = 8;
 constexpr int kMaxMem = 64;
 
-__device__ __forceinline__ float wave_max(float v) {
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // <a, b> over n floats, products and sum in fp64 (a product of two floats is exact there).  A score of +-80 carries an absolute error
 // of 1e-5 when it is summed in fp32, which the exponential turns into a relative error of the weight; and the two backward launches
 // recompute the scores in different orders, which fp64 makes agree to the last float bit in all but rare ties.
@@ -65,17 +55,6 @@ __device__ __forceinline__ double dot64(const float* a, const float* b, int n) {
     double s = 0.0;
     for (int d = 0; d < n; ++d) s = fma((double)a[d], (double)b[d], s);
     return s;
-}
-
-// 64 values, one per lane, sorted descending over the lanes (bitonic network of xor shuffles; every lane takes part)
-__device__ __forceinline__ float wave_sort_desc(float v, int lane) {
-    for (int k = 2; k <= 64; k <<= 1)
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            const float u = __shfl_xor(v, j, 64);
-            const bool keep_max = ((lane & k) == 0) == ((lane & j) == 0);
-            v = keep_max ? fmaxf(v, u) : fminf(v, u);
-        }
-    return v;
 }
 
 __device__ __forceinline__ float weight_of(bool soft, bool live, float z, float mx, float t) {
@@ -121,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void seg_attn_fwd_wave_kernel(int32_t H, in
             const float* kr = kL + lane * ld + h * dk;
             z = (float)(dot64(qr, kr, dk) * (double)scale);
         }
-        const float mx = wave_max(z);
+        const float mx = dn_wave_max(z);
         if ((q_skip != nullptr && q_skip[row] != 0) || mx == -INFINITY) {
             for (int d = lane; d < dk; d += 64) orow[d] = 0.f;
             if (lane == 0) { st[0] = 0.f; st[1] = kSoft ? 1.f : 0.f; }
@@ -130,20 +109,11 @@ __global__ __launch_bounds__(kBlock) void seg_attn_fwd_wave_kernel(int32_t H, in
         float p, t1;
         if (kSoft) {
             const float e = live ? expf(z - mx) : 0.f;
-            t1 = wave_sum(e);
+            t1 = dn_wave_sum(e);
             p = e / t1;
         } else {
             const float zc = z - mx;                                   // (-inf on the lanes without a live key)
-            const float s = wave_sort_desc(zc, lane);
-            const bool has = s > -INFINITY;
-            float cs = has ? s : 0.f;
-            for (int o = 1; o < 64; o <<= 1) {
-                const float u = __shfl_up(cs, o, 64);
-                if (lane >= o) cs += u;
-            }
-            const bool in = has && 1.f + (float)(lane + 1) * s > cs;
-            const int kk = __popcll(__ballot(in));                     // (>= 1: the first lane holds 0 and 1 > 0)
-            t1 = (__shfl(cs, kk - 1, 64) - 1.f) / (float)kk;
+            t1 = dn_sparsemax_tau_wave(zc, lane, DnSupportAct());
             p = live ? fmaxf(zc - t1, 0.f) : 0.f;
         }
         if (lane == 0) { st[0] = mx; st[1] = t1; }
@@ -202,64 +172,25 @@ __global__ __launch_bounds__(kBlock) void seg_attn_fwd_block_kernel(int32_t H, i
             if (!kSoft) srt[i] = z;
         }
         __syncthreads();
-        if (!kSoft) {
-            const int half = total >> 1, hn = n2 >> 1;
-            for (int k2 = 2; k2 <= n2; k2 <<= 1)
-                for (int j2 = k2 >> 1; j2 >= 1; j2 >>= 1) {
-                    for (int i = t; i < half; i += kBlock) {
-                        const int h = i / hn, ii = i - h * hn;
-                        const int a = ((ii & ~(j2 - 1)) << 1) | (ii & (j2 - 1));
-                        float* s = srt + (size_t)h * n2;
-                        const float x = s[a], y = s[a | j2];
-                        const bool desc = (a & k2) == 0;
-                        if ((x < y) == desc) { s[a] = y; s[a | j2] = x; }
-                    }
-                    __syncthreads();
-                }
-        }
+        if (!kSoft) dn_sort_desc_lists<kBlock>(srt, heads, n2, t);
         // threshold (or maximum and sum) per head: wave w takes the heads w, w + kWaves
         for (int h = w; h < heads; h += kWaves) {
             if (kSoft) {
                 float m = -INFINITY;
                 for (int j = lane; j < n2; j += 64) m = fmaxf(m, sc[h * n2 + j]);
-                m = wave_max(m);
+                m = dn_wave_max(m);
                 float s = 0.f;
                 if (m > -INFINITY)
                     for (int j = lane; j < n2; j += 64) {
                         const float z = sc[h * n2 + j];
                         if (z > -INFINITY) s += expf(z - m);
                     }
-                s = wave_sum(s);
+                s = dn_wave_sum(s);
                 if (lane == 0) { hm[h] = m; ht[h] = s; }
             } else {
-                const float* s = srt + (size_t)h * n2;
-                const float m = s[0];
-                const int C = n2 >> 6;                                 // (n2 >= 128 in this class)
-                float ls = 0.f;
-                if (m > -INFINITY)
-                    for (int c = 0; c < C; ++c) {
-                        const float x = s[lane * C + c];
-                        if (x > -INFINITY) ls += x - m;
-                    }
-                float cs = ls;                                         // inclusive scan of the lanes' chunk sums
-                for (int o = 1; o < 64; o <<= 1) {
-                    const float u = __shfl_up(cs, o, 64);
-                    if (lane >= o) cs += u;
-                }
-                cs -= ls;
-                float cnt = 0.f, ssum = 0.f;
-                if (m > -INFINITY)
-                    for (int c = 0; c < C; ++c) {
-                        const float x = s[lane * C + c];
-                        if (x > -INFINITY) {
-                            const float zc = x - m;
-                            cs += zc;
-                            if (1.f + (float)(lane * C + c + 1) * zc > cs) { cnt += 1.f; ssum += zc; }
-                        }
-                    }
-                cnt = wave_sum(cnt);
-                ssum = wave_sum(ssum);
-                if (lane == 0) { hm[h] = m; ht[h] = cnt > 0.f ? (ssum - 1.f) / cnt : 0.f; }
+                float m, tau;
+                dn_sparsemax_tau_sorted(srt + (size_t)h * n2, n2, lane, DnSupportAct(), m, tau);
+                if (lane == 0) { hm[h] = m; ht[h] = tau; }
             }
         }
         __syncthreads();
@@ -334,8 +265,8 @@ __global__ __launch_bounds__(kBlock) void seg_attn_bwd_q_kernel(int32_t H, int32
                 else if (p > 0.f) { s1 += dp; cnt += 1.f; }
             }
         }
-        s1 = wave_sum(s1);
-        cnt = wave_sum(cnt);
+        s1 = dn_wave_sum(s1);
+        cnt = dn_wave_sum(cnt);
         const double term = kSoft ? s1 : (cnt > 0.f ? s1 / (double)cnt : 0.0);
         __syncthreads();                                               // pw / dw of the wave are written
         if (active) {
@@ -345,7 +276,7 @@ __global__ __launch_bounds__(kBlock) void seg_attn_bwd_q_kernel(int32_t H, int32
                 if (!skipped)
                     for (int j = 0; j < klen; ++j) {
                         const float p = pw[j];
-                        const float dz = kSoft ? p * (float)(dw[j] - term) : (p > 0.f ? (float)(dw[j] - term) : 0.f);
+                        const float dz = dn_score_dz(kSoft, p, (float)(dw[j] - term));
                         if (dz != 0.f) acc = fmaf(dz, k[(size_t)(k0 + j) * H + h * dk + d], acc);
                     }
                 dq[(size_t)row * H + h * dk + d] = acc * scale;
@@ -403,7 +334,7 @@ __global__ __launch_bounds__(kBlock) void seg_attn_bwd_kv_kernel(int32_t H, int3
         if (!live) continue;
         const size_t s = (size_t)i * heads + h;
         const float p = weight_of(kSoft, true, (float)(z * (double)scale), stat[s * 2], stat[s * 2 + 1]);
-        const float dz = kSoft ? p * (float)(dp - rterm[s]) : (p > 0.f ? (float)(dp - rterm[s]) : 0.f);
+        const float dz = dn_score_dz(kSoft, p, (float)(dp - rterm[s]));
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             av[c] = fmaf(p, gv[c], av[c]);
@@ -530,21 +461,7 @@ int check_attn(const char* what, int64_t B, int64_t Nq, int64_t Nk, int32_t H, i
     DN_REQUIRE(pow2(H / heads), "%s: the head width hidden / heads must be a power of two (got %d)", what, H / heads);
     DN_REQUIRE(max_k >= 1 && max_k <= kBlockKeys, "%s: key count over the class limit: 1 <= max_k <= %d (got %d)", what, kBlockKeys, max_k);
     DN_REQUIRE(max_q >= 1 && dn_cdiv(max_q, kBwdQTile) <= 65535, "%s: bad max_q (got %d)", what, max_q);
-    DN_REQUIRE(score == DN_SCORE_SPARSEMAX || score == DN_SCORE_SOFTMAX, "%s: bad score function %d", what, score);
-    return DN_OK;
-}
-
-int next_pow2(int x) {
-    int n = 128;
-    while (n < x) n <<= 1;
-    return n;
-}
-
-template <typename K>
-int allow_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024)
-        DN_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return DN_OK;
+    return dn_check_score(what, score);
 }
 
 }  // namespace
@@ -565,14 +482,14 @@ int dn_seg_attn_fwd_f32(int64_t B, int64_t Nq, int64_t Nk, int32_t H, int32_t he
         const size_t lds = (size_t)2 * max_k * (H + 1) * sizeof(float);
         const dim3 grid((unsigned)B, (unsigned)dn_cdiv(max_q, kWaveQTile));
         auto kern = soft ? seg_attn_fwd_wave_kernel<true> : seg_attn_fwd_wave_kernel<false>;
-        if (int rc = allow_lds(kern, lds)) return rc;
+        if (int rc = dn_allow_lds(kern, lds)) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, H, heads, max_k, q_ptr, k_ptr, q_skip, k_skip, q, k, v, scale, out, stat);
     } else {
-        const int n2 = next_pow2(max_k);
+        const int n2 = dn_pow2_at_least(128, max_k);
         const size_t lds = ((size_t)2 * heads * n2 + 2 * kMaxHeads) * sizeof(float);
         const dim3 grid((unsigned)B, (unsigned)dn_cdiv(max_q, kBlockQTile));
         auto kern = soft ? seg_attn_fwd_block_kernel<true> : seg_attn_fwd_block_kernel<false>;
-        if (int rc = allow_lds(kern, lds)) return rc;
+        if (int rc = dn_allow_lds(kern, lds)) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, H, heads, n2, q_ptr, k_ptr, q_skip, k_skip, q, k, v, scale, out, stat);
     }
     DN_CHECK_LAUNCH();

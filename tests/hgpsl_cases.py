@@ -105,25 +105,39 @@ def run_stack(device, dtype=torch.float32):
 
 # ---------------------------------------------------------------------------------------------- the structure batch of the GPU test
 STRUCT_SIZES = [1, 78, 0, 80, 81, 1280, 1281]          # ratio 0.8: k = 1, 63, 0, 64, 65, 1024, 1025
+STRUCT_SCALE = [1.0, 1.0, 1.0, 1.0, 1.0, 6.0, 6.0]      # the factor on the rows of each graph
 STRUCT_SEED0 = {6: 1000, 128: 2000}                      # where the seed search for the sparsemax margin starts, per H
 
+# The batches of the structure test: graph sizes, row factors, the first seed per H, and what the batch must come to at ratio 0.8
+# (kept sizes, the graphs of the composed fallback, the largest key count of each kernel class).  The block class sorts every row of
+# a launch at n2 = the launch's largest key count rounded up to a power of two (at least 128): "classes" meets n2 = 1024 with rows of
+# 65, 1024 keys, "mid-512" n2 = 512 with rows of 129 and of 257 keys, "mid-256" n2 = 256.
+STRUCT_BATCHES = {
+    "classes": dict(sizes=STRUCT_SIZES, scale=STRUCT_SCALE, seed0=STRUCT_SEED0, ks=[1, 63, 0, 64, 65, 1024, 1025], big=[6], max_wave=64,
+                    max_block=1024),
+    "mid-512": dict(sizes=[161, 321], scale=[3.0, 3.0], seed0={6: 3000, 128: 3000}, ks=[129, 257], big=[], max_wave=0, max_block=257),
+    "mid-256": dict(sizes=[161], scale=[3.0], seed0={6: 3000, 128: 3000}, ks=[129], big=[], max_wave=0, max_block=129),
+}
 
-def structure_batch(H, seed):
+
+def structure_batch(H, seed, sizes=STRUCT_SIZES, scale=STRUCT_SCALE):
     """x [N, H], edge_index (unique pairs, about 3 per node, some self loops, shuffled), weights [E], ptr, att [1, 2 H], distinct
-    integer scores (exact in any precision, so every path selects the same nodes) -- all float32 on the CPU.  The rows of the two large
+    integer scores (exact in any precision, so every path selects the same nodes) -- all float32 on the CPU.  The rows of the large
     graphs are scaled up: their logits spread, which is what lets EVERY one of a thousand rows keep the 1e-3 support margin."""
     rng = np.random.default_rng(seed)
-    ptr = [0] + np.cumsum(STRUCT_SIZES).tolist()
+    ptr = [0] + np.cumsum(sizes).tolist()
     N = ptr[-1]
     pairs = set()
-    for g, n in enumerate(STRUCT_SIZES):
+    for g, n in enumerate(sizes):
         for _ in range(3 * n):
             a, b = rng.integers(n, size=2)
             pairs.add((ptr[g] + int(a), ptr[g] + int(b)))
     pairs = sorted(pairs)
     ei = np.asarray([pairs[int(i)] for i in rng.permutation(len(pairs))], dtype=np.int64).T
     x = rng.standard_normal((N, H)).astype(np.float32)
-    x[ptr[5]:] *= 6.0
+    for g, factor in enumerate(scale):
+        if factor != 1.0:
+            x[ptr[g]:ptr[g + 1]] *= factor
     w = rng.uniform(0.2, 2.0, size=ei.shape[1]).astype(np.float32)
     att = (rng.standard_normal((1, 2 * H)) / np.sqrt(H)).astype(np.float32)
     score = rng.permutation(N).astype(np.float32)

@@ -110,27 +110,26 @@ def test_topk_equals_a_stable_sort(ratio):
 
 
 # ---------------------------------------------------------------------------------------------- structure learning
-@pytest.mark.parametrize("H", [6, 128])
-@pytest.mark.parametrize("weights", [True, False], ids=["weights", "ones"])
-@pytest.mark.parametrize("sparse", [False, True], ids=["softmax", "sparsemax"])
-def test_structure_forward_and_backward(sparse, weights, H):
+def _structure_case(batch, sparse, weights, H):
     ops = _ops()
     assert (ops.HGPSL_WAVE_KEYS, ops.HGPSL_MAX_KEYS) == (64, 1024)
     lamb, slope, ratio = 0.5, 0.2, 0.8
-    for seed in range(C.STRUCT_SEED0[H], C.STRUCT_SEED0[H] + 50):               # (sparsemax: seeded until the support margin holds)
-        b = C.structure_batch(H, seed)
+    spec = C.STRUCT_BATCHES[batch]
+    for seed in range(spec["seed0"][H], spec["seed0"][H] + 50):                 # (sparsemax: seeded until the support margin holds)
+        b = C.structure_batch(H, seed, spec["sizes"], spec["scale"])
         perm, pptr, ref, (xr, ar, wr) = C.structure_reference(b, sparse, weights, lamb, slope, ratio)
         if not sparse or ref["support_margin"] > 1e-3:
             break
     assert not sparse or ref["support_margin"] > 1e-3
-    assert np.diff(pptr).tolist() == [1, 63, 0, 64, 65, 1024, 1025]
+    assert np.diff(pptr).tolist() == spec["ks"]
     want = R.flat_blocks(ref["blocks"])
     coef = torch.from_numpy(np.random.default_rng(seed).standard_normal(want.numel()))
     (coef * want).sum().backward()
     ei = b["edge_index"].to(DEV)
     index = ops.HgpslIndex(ei[0], ei[1], torch.tensor(b["ptr"], device=DEV), b["x"].shape[0])
     pooled = index.pooled(ratio)
-    assert pooled.ptr_host == pptr and pooled.big == [6] and pooled.max_wave == 64 and pooled.max_block == 1024
+    assert pooled.ptr_host == pptr and pooled.big == spec["big"]
+    assert pooled.max_wave == spec["max_wave"] and pooled.max_block == spec["max_block"]
 
     def run(fused):
         with ops.hgpsl_fused(fused):
@@ -161,6 +160,23 @@ def test_structure_forward_and_backward(sparse, weights, H):
     print({k: "%.1e" % v for k, v in errs.items()})
     for a, c in zip(fused, again):                                            # the same bits on the second run
         assert (a is None and c is None) or torch.equal(a, c)
+
+
+@pytest.mark.parametrize("H", [6, 128])
+@pytest.mark.parametrize("weights", [True, False], ids=["weights", "ones"])
+@pytest.mark.parametrize("sparse", [False, True], ids=["softmax", "sparsemax"])
+def test_structure_forward_and_backward(sparse, weights, H):
+    assert C.STRUCT_BATCHES["classes"]["ks"] == [1, 63, 0, 64, 65, 1024, 1025]
+    _structure_case("classes", sparse, weights, H)
+
+
+@pytest.mark.parametrize("H", [6, 128])
+@pytest.mark.parametrize("weights", [True, False], ids=["weights", "ones"])
+@pytest.mark.parametrize("sparse", [False, True], ids=["softmax", "sparsemax"])
+@pytest.mark.parametrize("batch", ["mid-512", "mid-256"])
+def test_structure_between_the_class_limits(batch, sparse, weights, H):
+    """The same over batches whose block-class launch sorts at n2 = 512 and at n2 = 256 (the batch above only meets n2 = 1024)."""
+    _structure_case(batch, sparse, weights, H)
 
 
 # ---------------------------------------------------------------------------------------------- the goldens under both paths
