@@ -222,6 +222,13 @@ _SIGS = {
     "dn_hgpsl_structure_bwd_cols_f32": (ctypes.c_int, [c_i64] * 4 + [P] * 6 + [P]),
     "dn_hgpsl_structure_bwd_edges_f32": (ctypes.c_int, [c_i64] * 5 + [c_i32] + [P] * 9 + [c_f32, P, P]),
     "dn_hgpsl_att_grad_f32": (ctypes.c_int, [c_i64, c_i32] + [P] * 5 + [P]),
+    "dn_eseq_filter_max_labels": (c_i32, []),
+    "dn_eseq_conv_pool_fwd_f32": (ctypes.c_int, [c_i64] + [c_i32] * 5 + [c_f32, c_i32] + [P] * 8 + [P]),
+    "dn_eseq_dconv_f32": (ctypes.c_int, [c_i64] + [c_i32] * 5 + [c_f32] + [P] * 4 + [P]),
+    "dn_eseq_dgrad_f32": (ctypes.c_int, [c_i64] + [c_i32] * 5 + [P] * 6 + [P]),
+    "dn_eseq_wgrad_f32": (ctypes.c_int, [c_i64] + [c_i32] * 4 + [P] * 4 + [c_i32, P, P] + [P]),
+    "dn_eseq_wgrad_combine_f32": (ctypes.c_int, [c_i32, c_i32, c_i32] + [P] * 4 + [P]),
+    "dn_eseq_filter_gate_i64": (ctypes.c_int, [c_i64, c_i32, c_i32] + [P] * 7 + [P]),
 }
 
 _lib = None

@@ -5499,3 +5499,176 @@ def hgpsl_compact(blocks, pooled):
     off = nz - pooled.blk_ptr.index_select(0, g)
     r = torch.div(off, k.clamp(min=1), rounding_mode="floor")
     return torch.stack([c0 + r, c0 + off - r * k]), blocks.index_select(0, nz)
+
+
+# ----------------------------------------------------------------------------------------------
+# The CNN count model on edge sequences: conv -> act -> max pool -> gate (-> residual) per layer, and the label filter (dn_eseq.hip)
+# ----------------------------------------------------------------------------------------------
+ESEQ_MAX_C = 128
+ESEQ_MAX_K = 5
+ESEQ_MAX_B = 65535                                               # sequences of a launch (the grid's second dimension)
+ESEQ_ACTS = {"none": 0, "relu": 1, "leaky_relu": 2}
+ESEQ_LEAKY_SLOPE = 1 / 5.5                                       # the reference's leaky_relu slope (act.LEAKY_RELU_A, constants.py:10)
+ESEQ_WGRAD_SLICES = 128                                          # slices of the batch whose weight-gradient partials are kept apart
+
+# The model's default.  Measured on the scale batch (docs/LAB_NOTES.md "SI count models: CNN"; 512 pairs, H = 64, graph sequences of
+# 302 tuples, fused and composed alternated in one process, 4 rounds): the layer step 0.52 against 0.97 ms (k = 2) and 0.68 against
+# 1.11 ms (k = 3), the model step 5.6 against 8.6 ms and 6.1 against 9.3 ms, every fused round faster than every composed round -- so
+# by the project's rule the kernels are the default (as HGT_FUSED_DEFAULT).
+ESEQ_FUSED_DEFAULT = True
+
+
+def eseq_fused_enabled():
+    return eseq_fused.override(ESEQ_FUSED_DEFAULT)
+
+
+class eseq_fused(_ThreadSwitch):
+    """Context manager: EdgeSeqModel forwards started inside it (on this thread) run the label filter, the code embedding and the
+    CNN layers on the HIP kernels (on=True) where the predicates allow it, or on the composed path (on=False: torch ops)."""
+    _slot = "eseq_fused"
+
+
+def eseq_out_lens(L, k, padding, stride=1):
+    """(L1, L2): the conv rows and the outputs of a layer on sequences of L positions."""
+    L1 = (L + 2 * padding - k) // stride + 1
+    return L1, L1 + 2 * padding - k // stride + 1
+
+
+def eseq_fused_supported(x, weight, padding, act, stride=1, dilation=1, groups=1):
+    """The predicate of eseq_conv_pool's kernels: fp32 on the GPU, C_in == C_out a multiple of 16 in 16 .. 128, 2 <= k <= 5,
+    0 <= padding <= k // 2, stride = dilation = groups = 1, act in relu | leaky_relu | none, at least one output position, at most 65 535 sequences."""
+    if weight.dim() != 3 or x.dim() != 3:
+        return False
+    Co, Ci, k = (int(s) for s in weight.shape)
+    return (x.is_cuda and weight.is_cuda and x.dtype == weight.dtype == torch.float32 and Co == Ci == int(x.shape[2])
+            and Co % 16 == 0 and 16 <= Co <= ESEQ_MAX_C and 2 <= k <= ESEQ_MAX_K and 0 <= padding <= k // 2
+            and stride == 1 and dilation == 1 and groups == 1 and act in ESEQ_ACTS and 0 < x.shape[0] <= ESEQ_MAX_B
+            and x.shape[0] * (x.shape[1] + 2 * ESEQ_MAX_K) * ESEQ_MAX_C < 2 ** 31       # (the kernels' grids and 32-bit tile offsets)
+            and eseq_out_lens(int(x.shape[1]), k, padding)[1] >= 1)
+
+
+def _eseq_windows(x, k, p, fill):
+    return torch.nn.functional.pad(x, (0, 0, p, p), value=fill).unfold(1, k, 1)
+
+
+def eseq_conv_pool_composed(x, weight, bias, gate_in, padding, act, residual):
+    """eseq_conv_pool in torch ops on rows layout (any device and dtype; act: any name of the activation table)."""
+    from .subgraph_isomorphism.act import map_activation_str_to_layer
+    k, p = int(weight.shape[2]), int(padding)
+    g = gate_in.reshape(x.shape[0], x.shape[1], 1).to(x.dtype)
+    x0 = x * g
+    conv = torch.einsum("blcj,ocj->blo", _eseq_windows(x0, k, p, 0.0), weight) + bias
+    pooled = _eseq_windows(map_activation_str_to_layer(act)(conv), k, p, float("-inf")).max(dim=-1)[0]
+    g2 = _eseq_windows(_eseq_windows(g, k, p, float("-inf")).max(dim=-1)[0], k, p, float("-inf")).max(dim=-1)[0]
+    y = pooled * g2
+    if residual and y.shape == x0.shape:
+        y = y + x0
+    return y, g2
+
+
+class _EseqConvPoolFn(torch.autograd.Function):
+    """One CNN layer in rows layout.  forward: ONE kernel launch (dn_eseq_conv_pool_fwd_f32) behind a re-laid copy of the weight;
+    backward: FOUR (dconv gather, input gradient, weight-gradient partials, their in-order combine) behind a second re-laid copy.
+    No atomics: bit-identical from run to run."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gate, lo, padding, act, residual):
+        B, L, C = (int(s) for s in x.shape)
+        k = int(weight.shape[2])
+        L1, L2 = eseq_out_lens(L, k, padding)
+        wt = weight.permute(2, 1, 0).contiguous()                   # [j][ci][co]
+        y = torch.empty((B, L2, C), dtype=torch.float32, device=x.device)
+        gate_out = torch.empty((B, L2), dtype=torch.float32, device=x.device)
+        arg = torch.empty((B, L2, C), dtype=torch.uint8, device=x.device)
+        code = ESEQ_ACTS[act]
+        launch_tagged("eseq_conv_pool_fwd", lambda: check(lib().dn_eseq_conv_pool_fwd_f32(
+            B, L, C, k, padding, code, ESEQ_LEAKY_SLOPE, 1 if residual else 0, ptr(x), ptr(gate), ptr(wt), ptr(bias), ptr(lo), ptr(y),
+            ptr(gate_out), ptr(arg), stream_ptr()), "dn_eseq_conv_pool_fwd_f32"))
+        ctx.geo = (B, L, C, k, int(padding), code, bool(residual))
+        ctx.save_for_backward(x, weight, gate, lo, gate_out, arg)
+        ctx.mark_non_differentiable(gate_out)
+        return y, gate_out
+
+    @staticmethod
+    def backward(ctx, dy, _dgate):
+        x, weight, gate, lo, gate_out, arg = ctx.saved_tensors
+        B, L, C, k, p, code, residual = ctx.geo
+        L1, L2 = eseq_out_lens(L, k, p)
+        dy = dy.contiguous()
+        dev = x.device
+        dconv = torch.empty((B, L1, C), dtype=torch.float32, device=dev)
+        launch_tagged("eseq_dconv", lambda: check(lib().dn_eseq_dconv_f32(
+            B, L, C, k, p, code, ESEQ_LEAKY_SLOPE, ptr(dy), ptr(gate_out), ptr(arg), ptr(dconv), stream_ptr()), "dn_eseq_dconv_f32"))
+        dx = dW = db = None
+        if ctx.needs_input_grad[0]:
+            wd = weight.flip(2).permute(2, 0, 1).contiguous()       # [j][co][ci], j reversed
+            dx = torch.empty_like(x)
+            launch_tagged("eseq_dgrad", lambda: check(lib().dn_eseq_dgrad_f32(
+                B, L, C, k, p, 1 if residual else 0, ptr(dconv), ptr(dy), ptr(gate), ptr(wd), ptr(lo), ptr(dx), stream_ptr()),
+                "dn_eseq_dgrad_f32"))
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            G = max(1, min(ESEQ_WGRAD_SLICES, B * ((L1 + 31) // 32)))
+            part = torch.empty((G, k, C, C), dtype=torch.float32, device=dev)
+            part_b = torch.empty((G, C), dtype=torch.float32, device=dev)
+            launch_tagged("eseq_wgrad", lambda: check(lib().dn_eseq_wgrad_f32(
+                B, L, C, k, p, ptr(x), ptr(gate), ptr(dconv), ptr(lo), G, ptr(part), ptr(part_b), stream_ptr()), "dn_eseq_wgrad_f32"))
+            dW, db = torch.empty_like(weight), torch.empty((C,), dtype=torch.float32, device=dev)
+            launch_tagged("eseq_wgrad_combine", lambda: check(lib().dn_eseq_wgrad_combine_f32(
+                C, k, G, ptr(part), ptr(part_b), ptr(dW), ptr(db), stream_ptr()), "dn_eseq_wgrad_combine_f32"))
+        return dx, dW, db, None, None, None, None, None
+
+
+def eseq_conv_pool(x, lens, weight, bias, gate_in, padding, act, residual):
+    """One CNN layer on right-aligned sequences in rows layout: (y [B, L2, C], gate_out [B, L2, 1]) with x0 = x * gate_in,
+    y = maxpool_k(act(conv1d(x0, weight, bias, padding)), padding) * gate_out (+ x0 when residual and L2 == L) and gate_out = gate_in
+    through the same two max windows (DESIGN.md "SI count models: CNN").  x [B, L, C]; weight [C, C, k]; gate_in [B, L] or [B, L, 1],
+    0 / 1 floats; lens: B host integers -- every non-zero of gate_in lies in the last lens[b] positions of its row (None: no bound).
+    Gradients reach x, weight and bias.  The kernels where eseq_fused_supported holds, else eseq_conv_pool_composed."""
+    B, L = int(x.shape[0]), int(x.shape[1])
+    residual = bool(residual) and eseq_out_lens(L, int(weight.shape[2]), int(padding))[1] == L
+    if not eseq_fused_supported(x, weight, int(padding), act):
+        return launch_tagged("eseq_layer_composed", lambda: eseq_conv_pool_composed(x, weight, bias, gate_in, padding, act, residual))
+    lens = [L] * B if lens is None else [int(v) for v in lens]
+    if len(lens) != B or min(lens) < 0 or max(lens) > L:
+        raise _lib.DnHipError("eseq_conv_pool: lens needs one length in [0, L] per sequence")
+    lo = torch.tensor([L - v for v in lens], dtype=I32).to(x.device, non_blocking=True)
+    gate = gate_in.reshape(B, L).to(torch.float32).contiguous()
+    require_gpu(x, weight, bias, gate)
+    y, gate_out = _EseqConvPoolFn.apply(x.contiguous(), weight.contiguous(), bias.contiguous(), gate, lo, int(padding), act, residual)
+    return y, gate_out.unsqueeze(-1)
+
+
+def eseq_filter_max_labels():
+    """The cap of eseq_filter_gate's kernel: labels in [0, cap) fit its LDS bit sets (4096)."""
+    return int(lib().dn_eseq_filter_max_labels())
+
+
+def eseq_filter_supported(p_ul, p_el, p_vl, g_ul, g_el, g_vl, num_labels):
+    """int64 [B, Lp] / [B, Lg] label tensors on the GPU, and label tables of at most eseq_filter_max_labels() entries."""
+    ts = (p_ul, p_el, p_vl, g_ul, g_el, g_vl)
+    return (all(t.is_cuda and t.dtype == torch.int64 and t.dim() == 2 for t in ts) and p_ul.shape == p_el.shape == p_vl.shape
+            and g_ul.shape == g_el.shape == g_vl.shape and p_ul.shape[0] == g_ul.shape[0] and p_ul.numel() > 0 and g_ul.numel() > 0
+            and p_ul.shape[0] <= ESEQ_MAX_B and max(p_ul.numel(), g_ul.numel()) < 2 ** 31
+            and int(num_labels) <= eseq_filter_max_labels())
+
+
+def eseq_filter_gate_composed(p_ul, p_el, p_vl, g_ul, g_el, g_vl):
+    """get_filter_gate of the reference in torch ops: three ScalarFilters ([B, Lg, Lp] differences each), and-ed."""
+    def one(p_x, g_x):
+        return torch.max((g_x.unsqueeze(2) - p_x.unsqueeze(1)) == 0, dim=2)[0]
+    return (one(p_ul, g_ul) & one(p_vl, g_vl)) & one(p_el, g_el)
+
+
+def eseq_filter_gate(p_ul, p_el, p_vl, g_ul, g_el, g_vl):
+    """[B, Lg] bool: graph position (b, t) passes when each of its three labels occurs in the matching PADDED pattern row b (the
+    padded zeros count, as in the reference).  One launch of dn_eseq_filter_gate_i64; labels must lie in [0, eseq_filter_max_labels())
+    (eseq_filter_supported with the label table size; larger tables: eseq_filter_gate_composed)."""
+    ts = [t.contiguous() for t in (p_ul, p_el, p_vl, g_ul, g_el, g_vl)]
+    require_gpu(*ts)
+    if not eseq_filter_supported(*ts, num_labels=0):
+        raise _lib.DnHipError("eseq_filter_gate: int64 [B, Lp] / [B, Lg] label tensors on the GPU expected")
+    B, Lp, Lg = int(ts[0].shape[0]), int(ts[0].shape[1]), int(ts[3].shape[1])
+    out = torch.empty((B, Lg), dtype=torch.bool, device=ts[0].device)
+    launch_tagged("eseq_filter_gate", lambda: check(lib().dn_eseq_filter_gate_i64(B, Lp, Lg, *[ptr(t) for t in ts], ptr(out), stream_ptr()),
+                                                   "dn_eseq_filter_gate_i64"))
+    return out

@@ -13,3 +13,5 @@ from .graph_adj_v2 import CompGCN, DMPNN, GraphAdjModelV2  # noqa: F401
 from .lrp import LRP, LRPLayer  # noqa: F401
 from .dmplrp import DMPLRP, DMPLRPPoolLayer  # noqa: F401
 from .hgt import HGT, DecompMultiTransform, HeteroGraphTransLayer  # noqa: F401
+from .edge_seq import EdgeSeqModel  # noqa: F401
+from .cnn import CNN, CNNLayer  # noqa: F401

@@ -1301,6 +1301,38 @@ int dn_hgpsl_structure_bwd_edges_f32(int64_t B, int64_t N, int64_t E, int64_t Np
 int dn_hgpsl_att_grad_f32(int64_t Np, int32_t H, const float* xp, const float* dp, const float* dq, float* ws, float* datt,
                           dn_stream_t stream);
 
+/* ---- The CNN count model's layer on edge sequences (csrc/dn_eseq.hip), rows layout x [B, L, C], fp32.
+ *   C a multiple of 16 in 16 .. 128, 2 <= k <= 5, 0 <= padding <= k / 2, stride 1; L1 = L + 2 padding - k + 1 conv rows,
+ *   L2 = L1 + 2 padding - k + 1 outputs (>= 1).  act: 0 none, 1 relu, 2 leaky_relu(slope).  Sequences are right-aligned: lo [B] is
+ *   the first position of a sequence that may carry a non-zero gate_in; tiles left of a sequence's support are written as zeros
+ *   without being computed.  Every entry point checks its arguments on the host before it launches anything.
+ *   dn_eseq_conv_pool_fwd_f32   y [B, L2, C] = max-pool(act(conv(x * gate_in))) * gate_out (+ x * gate_in: residual, needs L2 == L),
+ *                        gate_out [B, L2] = gate_in through the two max windows, arg [B, L2, C] = the winning window slot (bits
+ *                        0-2, ties to the first) | 0x80 where the winning conv value is > 0 (undefined in the zero tiles).
+ *                        wt [k][C][C] = weight[co][ci][j] stored as [j][ci][co].
+ *   dn_eseq_dconv_f32    dconv [B, L1, C]: the gradient at the conv positions, gathered in slot order from dy, gate_out and arg.
+ *   dn_eseq_dgrad_f32    dx [B, L, C] = (dconv * W (+ dy: residual)) * gate_in; wd [k][C][C] = weight[co][ci][k - 1 - j] stored as
+ *                        [j][co][ci].
+ *   dn_eseq_wgrad_f32    part [num_slices][k][C][C] ([j][ci][co]) and part_b [num_slices][C]: per slice of the batch's 32-row conv
+ *                        tiles the sums of x0^T dconv and of dconv's columns.
+ *   dn_eseq_wgrad_combine_f32   dW [C][C][k], db [C]: the partials added in slice order.
+ *   dn_eseq_filter_gate_i64     out [B, Lg] (0 / 1) = g_ul in p_ul's row and g_el in p_el's and g_vl in p_vl's (the padded zeros of
+ *                        the pattern rows count); labels in [0, dn_eseq_filter_max_labels()), others never match. */
+int32_t dn_eseq_filter_max_labels(void);
+int dn_eseq_conv_pool_fwd_f32(int64_t B, int32_t L, int32_t C, int32_t k, int32_t padding, int32_t act, float slope, int32_t residual,
+                              const float* x, const float* gate_in, const float* wt, const float* bias, const int32_t* lo, float* y,
+                              float* gate_out, uint8_t* arg, dn_stream_t stream);
+int dn_eseq_dconv_f32(int64_t B, int32_t L, int32_t C, int32_t k, int32_t padding, int32_t act, float slope, const float* dy,
+                      const float* gate_out, const uint8_t* arg, float* dconv, dn_stream_t stream);
+int dn_eseq_dgrad_f32(int64_t B, int32_t L, int32_t C, int32_t k, int32_t padding, int32_t residual, const float* dconv, const float* dy,
+                      const float* gate_in, const float* wd, const int32_t* lo, float* dx, dn_stream_t stream);
+int dn_eseq_wgrad_f32(int64_t B, int32_t L, int32_t C, int32_t k, int32_t padding, const float* x, const float* gate_in,
+                      const float* dconv, const int32_t* lo, int32_t num_slices, float* part, float* part_b, dn_stream_t stream);
+int dn_eseq_wgrad_combine_f32(int32_t C, int32_t k, int32_t num_slices, const float* part, const float* part_b, float* dW, float* db,
+                              dn_stream_t stream);
+int dn_eseq_filter_gate_i64(int64_t B, int32_t Lp, int32_t Lg, const int64_t* p_ul, const int64_t* p_el, const int64_t* p_vl,
+                            const int64_t* g_ul, const int64_t* g_el, const int64_t* g_vl, uint8_t* out, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
