@@ -229,6 +229,9 @@ _SIGS = {
     "dn_eseq_wgrad_f32": (ctypes.c_int, [c_i64] + [c_i32] * 4 + [P] * 4 + [c_i32, P, P] + [P]),
     "dn_eseq_wgrad_combine_f32": (ctypes.c_int, [c_i32, c_i32, c_i32] + [P] * 4 + [P]),
     "dn_eseq_filter_gate_i64": (ctypes.c_int, [c_i64, c_i32, c_i32] + [P] * 7 + [P]),
+    "dn_eseq_rnn_saved_per_unit": (c_i32, [c_i32]),
+    "dn_eseq_rnn_fwd_f32": (ctypes.c_int, [c_i64] + [c_i32] * 5 + [P] * 9 + [P]),
+    "dn_eseq_rnn_bwd_f32": (ctypes.c_int, [c_i64] + [c_i32] * 4 + [P] * 8 + [P]),
 }
 
 _lib = None

@@ -3,6 +3,7 @@
 Everything here runs on the GPU through libdn_hip.so; PyTorch only supplies device memory, the
 current stream and autograd bookkeeping.  There is deliberately no CPU path.
 """
+import contextlib as _contextlib
 import ctypes
 import os as _os
 import threading as _threading
@@ -5672,3 +5673,170 @@ def eseq_filter_gate(p_ul, p_el, p_vl, g_ul, g_el, g_vl):
     launch_tagged("eseq_filter_gate", lambda: check(lib().dn_eseq_filter_gate_i64(B, Lp, Lg, *[ptr(t) for t in ts], ptr(out), stream_ptr()),
                                                    "dn_eseq_filter_gate_i64"))
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# The RNN count model on edge sequences: LSTM / GRU / tanh recurrence with the gate (and the residual) per layer (dn_eseq_rnn.hip)
+# ----------------------------------------------------------------------------------------------
+ESEQ_RNN_CELLS = {"LSTM": 0, "GRU": 1, "RNN": 2}
+ESEQ_RNN_GATES = {"LSTM": 4, "GRU": 3, "RNN": 1}
+ESEQ_RNN_WIDTHS = (16, 32, 48, 64)                               # hidden units per direction: W_hh stays in a workgroup's registers
+ESEQ_RNN_MAX_IN = 128
+
+# The RNN layers' default behind the same switch (`with ops.eseq_fused(on)`).  Measured on the scale batch (docs/LAB_NOTES.md "SI count
+# models: RNN"; 512 pairs, H = 64, graph sequences of 302 tuples, three paths alternated in one process, 3 rounds): the layer step
+# 3.54 ms fused against 11.4 ms on torch's module (MIOpen) at LSTM and 3.22 against 41.9 ms at GRU, the model step (3 layers) 14.3
+# against 53.8 ms and 13.6 against 116.7 ms; torch's native per-step kernels took 63 - 68 ms a layer step.  Every fused round was faster
+# than every composed round, so by the project's rule the kernels are the default.
+ESEQ_RNN_FUSED_DEFAULT = True
+
+
+# The composed path on the GPU: torch's own layer goes to MIOpen (False) or, with the cuDNN / MIOpen backend switched off around
+# the call, to torch's native per-step kernels (True).  MIOpen: it ran every test and was 1.6 - 5.8 times faster than the native path
+# on the scale batch (docs/LAB_NOTES.md "SI count models: RNN").  The one exception is made where it is needed (RNNLayer.forward): a
+# backward pass through a module in eval mode, which torch refuses on MIOpen.
+ESEQ_RNN_COMPOSED_NATIVE = False
+
+
+def eseq_rnn_fused_enabled():
+    return eseq_fused.override(ESEQ_RNN_FUSED_DEFAULT)
+
+
+def eseq_rnn_composed_backend(native=None):
+    """The context the composed path runs torch's recurrent layer in (native: None = ESEQ_RNN_COMPOSED_NATIVE)."""
+    if ESEQ_RNN_COMPOSED_NATIVE if native is None else native:
+        return torch.backends.cudnn.flags(enabled=False)
+    return _contextlib.nullcontext()
+
+
+def _eseq_rnn_names(bidirectional):
+    return [n + s for s in (("", "_reverse") if bidirectional else ("",)) for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
+
+
+def eseq_rnn_supported(x, params, cell, bidirectional):
+    """The predicate of eseq_rnn's kernels: fp32 on the GPU, cell in LSTM | GRU | RNN, hidden width per direction in {16, 32, 48, 64},
+    input width a multiple of 16 up to 128, 1 <= B <= 65535, L >= 1, and B L max(D 5 Hd, H) below 2^31 (the launches' 32-bit bound).
+    params: the torch module's tensors by name (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, and the _reverse set)."""
+    if cell not in ESEQ_RNN_CELLS or x.dim() != 3 or any(n not in params for n in _eseq_rnn_names(bidirectional)):
+        return False
+    G, D = ESEQ_RNN_GATES[cell], 2 if bidirectional else 1
+    B, L, H = (int(s) for s in x.shape)
+    w_hh = params["weight_hh_l0"]
+    Hd = int(w_hh.shape[1])
+    ts = [params[n] for n in _eseq_rnn_names(bidirectional)]
+    return (x.is_cuda and x.dtype == torch.float32 and all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+            and Hd in ESEQ_RNN_WIDTHS and H % 16 == 0 and 16 <= H <= ESEQ_RNN_MAX_IN
+            and tuple(params["weight_ih_l0"].shape) == (G * Hd, H) and tuple(w_hh.shape) == (G * Hd, Hd)
+            and 1 <= B <= ESEQ_MAX_B and L >= 1 and B * L * max(D * 5 * Hd, H) < 2 ** 31)
+
+
+def eseq_rnn_composed(x, params, gate, cell, bidirectional, residual, native=None):
+    """eseq_rnn on torch's own recurrent layer (any device and dtype): y = RNN(x * gate)[0] * gate (+ x * gate when residual and the
+    widths agree).  On the GPU torch sends the layer to MIOpen; native=True runs torch's per-step kernels instead (None: the module's
+    ESEQ_RNN_COMPOSED_NATIVE)."""
+    if cell not in ESEQ_RNN_CELLS:
+        raise ValueError("eseq_rnn: cell must be LSTM, GRU or RNN (got %r)" % (cell,))
+    g = gate.reshape(x.shape[0], x.shape[1], 1).to(x.dtype)
+    x0 = x * g
+    flat = [params[n] for n in _eseq_rnn_names(bidirectional)]
+    Hd = int(params["weight_hh_l0"].shape[1])
+    D = 2 if bidirectional else 1
+    h0 = x0.new_zeros((D, x.shape[0], Hd))
+    fn = {"LSTM": torch._VF.lstm, "GRU": torch._VF.gru, "RNN": torch._VF.rnn_tanh}[cell]
+    # (has_biases, num_layers, dropout, train, bidirectional, batch_first; train: torch refuses MIOpen's backward outside training mode)
+    args = (x0, (h0, h0) if cell == "LSTM" else h0, flat, True, 1, 0.0, True, bool(bidirectional), True)
+    with eseq_rnn_composed_backend(native if x.is_cuda else False):
+        o = fn(*args)[0]
+    y = o * g
+    return y + x0 if residual and y.shape == x0.shape else y
+
+
+class _EseqRnnFn(torch.autograd.Function):
+    """The recurrence of one layer.  forward: ONE launch (dn_eseq_rnn_fwd_f32) over P = x0 W_ih^T + b; backward: ONE launch
+    (dn_eseq_rnn_bwd_f32) for the pre-activation gradients, then per direction the W_hh gradient (and the GRU's b_hn) on the
+    deterministic row kernel.  dx, dW_ih and the folded biases follow through linear_any's own backward.  No atomics."""
+
+    @staticmethod
+    def forward(ctx, P, whh, bhn, x0, gate, lo, cell, D, Hd, residual):
+        B, L = int(P.shape[0]), int(P.shape[1])
+        code, dev = ESEQ_RNN_CELLS[cell], P.device
+        S = int(lib().dn_eseq_rnn_saved_per_unit(code))
+        y = torch.empty((B, L, D * Hd), dtype=torch.float32, device=dev)
+        h = torch.empty((B, L, D * Hd), dtype=torch.float32, device=dev)
+        sv = torch.empty((B, L, D, S * Hd), dtype=torch.float32, device=dev) if S else None
+        launch_tagged("eseq_rnn_fwd", lambda: check(lib().dn_eseq_rnn_fwd_f32(
+            B, L, Hd, D, code, 1 if residual else 0, ptr(P), ptr(whh), ptr(bhn), ptr(x0) if residual else None, ptr(gate), ptr(lo),
+            ptr(y), ptr(h), ptr(sv), stream_ptr()), "dn_eseq_rnn_fwd_f32"))
+        ctx.geo = (B, L, D, Hd, cell, bool(residual))
+        ctx.has_bhn = bhn is not None
+        ctx.save_for_backward(whh, gate, lo, h, sv)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        whh, gate, lo, h, sv = ctx.saved_tensors
+        B, L, D, Hd, cell, residual = ctx.geo
+        code, G, dev = ESEQ_RNN_CELLS[cell], ESEQ_RNN_GATES[cell], dy.device
+        dy = dy.contiguous()
+        dP = torch.empty((B, L, D * G * Hd), dtype=torch.float32, device=dev)
+        dhn = torch.empty((B, L, D * Hd), dtype=torch.float32, device=dev) if cell == "GRU" else None
+        launch_tagged("eseq_rnn_bwd", lambda: check(lib().dn_eseq_rnn_bwd_f32(
+            B, L, Hd, D, code, ptr(dy), ptr(gate), ptr(lo), ptr(whh), ptr(h), ptr(sv), ptr(dP), ptr(dhn), stream_ptr()),
+            "dn_eseq_rnn_bwd_f32"))
+        dwhh = dbhn = None
+        if ctx.needs_input_grad[1] or (ctx.has_bhn and ctx.needs_input_grad[2]):
+            def _wgrad():
+                _, chunks = _single_rel_table(B * L, dev)
+                zero = h.new_zeros((B, 1, Hd))
+                gw, gb = [], []
+                for d in range(D):
+                    hd = h[:, :, d * Hd:(d + 1) * Hd]
+                    prev = torch.cat([zero, hd[:, :-1]], 1) if d == 0 else torch.cat([hd[:, 1:], zero], 1)   # h of the step before
+                    a = dP[:, :, d * G * Hd:(d + 1) * G * Hd]
+                    if cell == "GRU":                             # the hidden side of n sits inside r * (W_hn h + b_hn)
+                        a = torch.cat([a[:, :, :2 * Hd], dhn[:, :, d * Hd:(d + 1) * Hd]], 2)
+                    w, cs = rows_wgrad_any(a.reshape(B * L, G * Hd), prev.reshape(B * L, Hd), chunks, 1, want_colsum=True)
+                    gw.append(w[0])
+                    gb.append(cs[0, 2 * Hd:] if cell == "GRU" else None)
+                return torch.stack(gw), (torch.stack(gb) if cell == "GRU" else None)
+            dwhh, dbhn = launch_tagged("eseq_rnn_wgrad", _wgrad)
+        return dP, dwhh, dbhn, (dy if residual else None), None, None, None, None, None, None
+
+
+def eseq_rnn(x, lens, params, gate, cell, bidirectional, residual):
+    """One RNN layer on right-aligned sequences in rows layout: y [B, L, D Hd] = RNN(x * gate)[0] * gate (+ x * gate when residual and
+    D Hd == H), the recurrent layer being torch's nn.LSTM / nn.GRU / nn.RNN(batch_first=True, bidirectional) with the tensors `params`
+    (a dict by torch's names: weight_ih_l0 [G Hd, H], weight_hh_l0 [G Hd, Hd], bias_ih_l0, bias_hh_l0, the _reverse set).  x [B, L, H];
+    gate [B, L] or [B, L, 1], 0 / 1 floats; lens: B host integers -- every non-zero of gate lies in the last lens[b] positions of its
+    row (None: no bound; only the reverse direction uses it).  Pad steps are computed, not skipped: the biases drive the state
+    through them.  Gradients reach x and every weight and bias.  The kernels where eseq_rnn_supported holds, else
+    eseq_rnn_composed (torch's own layer)."""
+    if cell not in ESEQ_RNN_CELLS:
+        raise ValueError("eseq_rnn: cell must be LSTM, GRU or RNN (got %r)" % (cell,))
+    if not eseq_rnn_supported(x, params, cell, bidirectional):
+        return launch_tagged("eseq_rnn_composed", lambda: eseq_rnn_composed(x, params, gate, cell, bidirectional, residual))
+    B, L, H = (int(s) for s in x.shape)
+    G, D, Hd = ESEQ_RNN_GATES[cell], 2 if bidirectional else 1, int(params["weight_hh_l0"].shape[1])
+    lens = [L] * B if lens is None else [int(v) for v in lens]
+    if len(lens) != B or min(lens) < 0 or max(lens) > L:
+        raise _lib.DnHipError("eseq_rnn: lens needs one length in [0, L] per sequence")
+    lo = torch.tensor([L - v for v in lens], dtype=I32).to(x.device, non_blocking=True)
+    g = gate.reshape(B, L).to(torch.float32).contiguous()
+    require_gpu(x, g)
+    residual = bool(residual) and D * Hd == H
+    sfx = ("", "_reverse")[:D]
+
+    def _proj():
+        x0 = x * g.unsqueeze(-1)
+        w_ih = torch.cat([params["weight_ih_l0" + s] for s in sfx], 0)
+        bs = []
+        for s in sfx:
+            b_ih, b_hh = params["bias_ih_l0" + s], params["bias_hh_l0" + s]
+            bs.append(torch.cat([b_ih[:2 * Hd] + b_hh[:2 * Hd], b_ih[2 * Hd:]]) if cell == "GRU" else b_ih + b_hh)
+        P = linear_any(x0.reshape(B * L, H), w_ih, torch.cat(bs), exact=True).view(B, L, D * G * Hd)
+        whh = torch.stack([params["weight_hh_l0" + s] for s in sfx])
+        bhn = torch.stack([params["bias_hh_l0" + s][2 * Hd:] for s in sfx]) if cell == "GRU" else None
+        return x0, P, whh, bhn
+
+    x0, P, whh, bhn = launch_tagged("eseq_rnn_proj", _proj)
+    return _EseqRnnFn.apply(P, whh, bhn, x0 if residual else None, g, lo, cell, D, Hd, residual)

@@ -15,3 +15,4 @@ from .dmplrp import DMPLRP, DMPLRPPoolLayer  # noqa: F401
 from .hgt import HGT, DecompMultiTransform, HeteroGraphTransLayer  # noqa: F401
 from .edge_seq import EdgeSeqModel  # noqa: F401
 from .cnn import CNN, CNNLayer  # noqa: F401
+from .rnn import RNN, RNNLayer  # noqa: F401

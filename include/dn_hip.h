@@ -1333,6 +1333,23 @@ int dn_eseq_wgrad_combine_f32(int32_t C, int32_t k, int32_t num_slices, const fl
 int dn_eseq_filter_gate_i64(int64_t B, int32_t Lp, int32_t Lg, const int64_t* p_ul, const int64_t* p_el, const int64_t* p_vl,
                             const int64_t* g_ul, const int64_t* g_el, const int64_t* g_vl, uint8_t* out, dn_stream_t stream);
 
+/* ---- The RNN count model's recurrence on edge sequences (csrc/dn_eseq_rnn.hip), rows layout, fp32.
+ *   cell: 0 LSTM (gates i f g o), 1 GRU (r z n), 2 tanh; G = 4 / 3 / 1 gates; Hd (hidden width per direction) in {16, 32, 48, 64};
+ *   D = 1 or 2 directions (direction 1 walks the time axis backwards); 1 <= B <= 65535, L >= 1, B L D 5 Hd < 2^31.
+ *   P [B, L, D G Hd]: the input side x0 W_ih^T + b, every bias folded in except the GRU's b_hn [D, Hd]; whh [D, G Hd, Hd]; gate [B, L]
+ *   (0 / 1); lo [B]: the first position of a sequence that may carry a non-zero gate (only direction 1 uses it: it stops at the
+ *   smallest lo of its 16 sequences and writes zeros to the left).  One workgroup per 16 sequences and direction walks all steps.
+ *   dn_eseq_rnn_fwd_f32   y [B, L, D Hd] = h gate (+ x0 [B, L, D Hd] when residual), h [B, L, D Hd] the ungated state, saved
+ *                         [B, L, D, S Hd] with S = dn_eseq_rnn_saved_per_unit(cell): LSTM i f g o c, GRU r z n (W_hn h + b_hn), tanh none.
+ *   dn_eseq_rnn_bwd_f32   dP [B, L, D G Hd]: the gradient at the input-side pre-activations; dhn [B, L, D Hd] (GRU only): the gradient
+ *                         at W_hn h + b_hn.  dy [B, L, D Hd] is the gradient at y (the gate is applied inside). */
+int32_t dn_eseq_rnn_saved_per_unit(int32_t cell);
+int dn_eseq_rnn_fwd_f32(int64_t B, int32_t L, int32_t Hd, int32_t D, int32_t cell, int32_t residual, const float* P, const float* whh,
+                        const float* bhn, const float* x0, const float* gate, const int32_t* lo, float* y, float* h, float* saved,
+                        dn_stream_t stream);
+int dn_eseq_rnn_bwd_f32(int64_t B, int32_t L, int32_t Hd, int32_t D, int32_t cell, const float* dy, const float* gate, const int32_t* lo,
+                        const float* whh, const float* h, const float* saved, float* dP, float* dhn, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
