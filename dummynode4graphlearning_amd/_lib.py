@@ -232,6 +232,10 @@ _SIGS = {
     "dn_eseq_rnn_saved_per_unit": (c_i32, [c_i32]),
     "dn_eseq_rnn_fwd_f32": (ctypes.c_int, [c_i64] + [c_i32] * 5 + [P] * 9 + [P]),
     "dn_eseq_rnn_bwd_f32": (ctypes.c_int, [c_i64] + [c_i32] * 4 + [P] * 8 + [P]),
+    "dn_txl_attn_fwd_f32": (ctypes.c_int, [c_i64] + [c_i32] * 6 + [c_f32] + [P] * 10 + [P]),
+    "dn_txl_attn_bwd_f32": (ctypes.c_int, [c_i64] + [c_i32] * 6 + [c_f32] + [P] * 18 + [P]),
+    "dn_txl_fold_mem_f32": (ctypes.c_int, [c_i64] + [c_i32] * 5 + [P] * 4 + [P]),
+    "dn_txl_reduce_rk_f32": (ctypes.c_int, [c_i64] + [c_i32] * 6 + [P] * 2 + [P]),
 }
 
 _lib = None

@@ -5840,3 +5840,142 @@ def eseq_rnn(x, lens, params, gate, cell, bidirectional, residual):
 
     x0, P, whh, bhn = launch_tagged("eseq_rnn_proj", _proj)
     return _EseqRnnFn.apply(P, whh, bhn, x0 if residual else None, g, lo, cell, D, Hd, residual)
+
+
+# ----------------------------------------------------------------------------------------------
+# The TransformerXL count model on edge sequences: relative-position attention over a sliding memory (dn_txl.hip)
+# ----------------------------------------------------------------------------------------------
+TXL_HEAD_WIDTHS = (16, 32, 64)
+TXL_MAX_SEG = 64
+TXL_MAX_WINDOW = 128
+
+# The TXL layers' default behind the same switch (`with ops.eseq_fused(on)`).  Measured on the scale batch (docs/LAB_NOTES.md "SI count
+# models: TXL"; 512 pairs, H = 64, graph sequences of 302 tuples = 5 segments, the two paths alternated in one process, 3 rounds of 10
+# steps): the layer step 5.81 ms fused against 11.30 ms composed at 1 head and 6.17 against 13.70 ms at 4 heads, the model step (3
+# layers) 24.97 against 42.52 ms and 26.16 against 50.28 ms.  Every fused round was faster than every composed round on both settings,
+# so by the project's rule the kernels are the default.
+TXL_FUSED_DEFAULT = True
+
+
+def txl_fused_enabled():
+    return eseq_fused.override(TXL_FUSED_DEFAULT)
+
+
+def txl_windows(Lp, seg_len, mem_len):
+    """[(first key row, memory rows, first query row)] per segment: segment s attends [s seg - mlen, (s + 1) seg), mlen = min(mem, s seg)."""
+    return [(s * seg_len - min(mem_len, s * seg_len), min(mem_len, s * seg_len), s * seg_len) for s in range(Lp // seg_len)]
+
+
+def txl_attention_supported(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len, mem_len):
+    """The predicate of txl_attention's kernels: fp32 on the GPU, q / k / v (/ k_mem / v_mem) [B, Lp, n, d] with d in {16, 32, 64},
+    seg_len in {16, 32, 48, 64}, Lp a multiple of it, mem_len a multiple of 16 (narrower than "any memory": a window is whole 16-key
+    tiles) with seg_len + mem_len <= 128, rk [P >= seg_len + mem_len, n, d], biases [n, d], sizes below 2^31."""
+    if q.dim() != 4:
+        return False
+    B, Lp, n, d = (int(s) for s in q.shape)
+    seg_len, mem_len = int(seg_len), int(mem_len)
+    ts = [q, k, v, rk, r_w_bias, r_r_bias] + ([k_mem, v_mem] if mem_len > 0 else [])
+    if any(t is None for t in ts) or not all(t.is_cuda and t.dtype == torch.float32 for t in ts):
+        return False
+    P = int(rk.shape[0])
+    return (d in TXL_HEAD_WIDTHS and seg_len % 16 == 0 and 16 <= seg_len <= TXL_MAX_SEG and mem_len >= 0 and mem_len % 16 == 0
+            and seg_len + mem_len <= TXL_MAX_WINDOW and B >= 1 and Lp >= seg_len and Lp % seg_len == 0
+            and all(tuple(t.shape) == (B, Lp, n, d) for t in ts[:3] + ts[6:]) and tuple(rk.shape) == (P, n, d) and P >= seg_len + mem_len
+            and tuple(r_w_bias.shape) == (n, d) and tuple(r_r_bias.shape) == (n, d) and Lp // seg_len <= 65535 and n <= 65535
+            and B * Lp * n * d < 2 ** 31 and B * (Lp // seg_len) * n * P * d < 2 ** 31)
+
+
+def txl_rel_shift(x):
+    """The reference's rel_shift on [B, qlen, klen, n]: pad a zero column, view as [klen + 1, qlen], drop the first row, view back."""
+    B, ql, kl, n = x.shape
+    x = torch.cat([x.new_zeros((B, ql, 1, n)), x], dim=2).view(B, kl + 1, ql, n)
+    return x[:, 1:].reshape(B, ql, kl, n)
+
+
+def txl_attention_composed(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len, mem_len, scale):
+    """txl_attention in torch ops, segment by segment (any device and dtype)."""
+    B, Lp, n, d = q.shape
+    outs = []
+    for k0, mlen, q0 in txl_windows(int(Lp), int(seg_len), int(mem_len)):
+        qs = q[:, q0:q0 + seg_len]
+        ks, vs = k[:, q0:q0 + seg_len], v[:, q0:q0 + seg_len]
+        if mlen > 0:
+            ks, vs = torch.cat([k_mem[:, k0:q0], ks], 1), torch.cat([v_mem[:, k0:q0], vs], 1)
+        klen = seg_len + mlen
+        ac = torch.einsum("bind,bjnd->bijn", qs + r_w_bias, ks)
+        bd = txl_rel_shift(torch.einsum("bind,jnd->bijn", qs + r_r_bias, rk[:klen].flip(0)))
+        prob = torch.softmax((ac + bd) * scale, dim=2)
+        outs.append(torch.einsum("bijn,bjnd->bind", prob, vs).reshape(B, seg_len, n * d))
+    return torch.cat(outs, 1)
+
+
+class _TxlAttnFn(torch.autograd.Function):
+    """forward: ONE launch (dn_txl_attn_fwd_f32).  backward: dn_txl_attn_bwd_f32, then the two fixed-order sums (the memory rows'
+    gradient, d rk); the bias gradients are the row sums of the two parts of dq.  No atomics."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, k_mem, v_mem, rk, rwb, rrb, seg, mem, scale):
+        B, Lp, n, d = (int(s) for s in q.shape)
+        P = int(rk.shape[0])
+        q, k, v, rk, rwb, rrb = (t.contiguous() for t in (q, k, v, rk, rwb, rrb))
+        k_mem, v_mem = (k_mem.contiguous(), v_mem.contiguous()) if mem > 0 else (None, None)
+        require_gpu(q, k, v, k_mem, v_mem, rk, rwb, rrb)
+        out = torch.empty((B, Lp, n * d), dtype=torch.float32, device=q.device)
+        stats = torch.empty((B, Lp, n, 2), dtype=torch.float32, device=q.device)
+        launch_tagged("txl_attn_fwd", lambda: check(lib().dn_txl_attn_fwd_f32(
+            B, Lp, n, d, seg, mem, P, scale, ptr(q), ptr(k), ptr(v), ptr(k_mem), ptr(v_mem), ptr(rk), ptr(rwb), ptr(rrb), ptr(out),
+            ptr(stats), stream_ptr()), "dn_txl_attn_fwd_f32"))
+        ctx.geo = (B, Lp, n, d, P, seg, mem, scale)
+        ctx.save_for_backward(q, k, v, k_mem, v_mem, rk, rwb, rrb, out, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, k_mem, v_mem, rk, rwb, rrb, out, stats = ctx.saved_tensors
+        B, Lp, n, d, P, seg, mem, scale = ctx.geo
+        S, dev = Lp // seg, dout.device
+        dout = dout.contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        dq_ac, dq_bd, dk, dv = new(B, Lp, n, d), new(B, Lp, n, d), new(B, Lp, n, d), new(B, Lp, n, d)
+        k_part, v_part = (new(B, S, n, mem, d), new(B, S, n, mem, d)) if mem > 0 else (None, None)
+        rk_part = new(B, S, n, P, d)
+
+        def _bwd():
+            check(lib().dn_txl_attn_bwd_f32(
+                B, Lp, n, d, seg, mem, P, scale, ptr(dout), ptr(q), ptr(k), ptr(v), ptr(k_mem), ptr(v_mem), ptr(rk), ptr(rwb), ptr(rrb),
+                ptr(out), ptr(stats), ptr(dq_ac), ptr(dq_bd), ptr(dk), ptr(dv), ptr(k_part), ptr(v_part), ptr(rk_part), stream_ptr()),
+                "dn_txl_attn_bwd_f32")
+            dkm = dvm = None
+            if mem > 0 and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]):
+                dkm, dvm = new(B, Lp, n, d), new(B, Lp, n, d)
+                check(lib().dn_txl_fold_mem_f32(B, Lp, n, d, seg, mem, ptr(k_part), ptr(v_part), ptr(dkm), ptr(dvm), stream_ptr()),
+                      "dn_txl_fold_mem_f32")
+            drk = None
+            if ctx.needs_input_grad[5]:
+                drk = new(P, n, d)
+                check(lib().dn_txl_reduce_rk_f32(B, Lp, n, d, seg, mem, P, ptr(rk_part), ptr(drk), stream_ptr()), "dn_txl_reduce_rk_f32")
+            return dkm, dvm, drk
+
+        dkm, dvm, drk = launch_tagged("txl_attn_bwd", _bwd)
+        need = ctx.needs_input_grad
+        return (dq_ac + dq_bd if need[0] else None, dk if need[1] else None, dv if need[2] else None, dkm if need[3] else None,
+                dvm if need[4] else None, drk, dq_ac.sum((0, 1)) if need[6] else None, dq_bd.sum((0, 1)) if need[7] else None,
+                None, None, None)
+
+
+def txl_attention(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len, mem_len, scale):
+    """TransformerXL's relative-position attention of one layer over the whole padded sequence: out [B, Lp, n d].  q, k, v [B, Lp, n, d]:
+    the projections of every row; k_mem, v_mem [B, Lp, n, d]: the same rows as the MEMORY sees them (in the model: projected from the
+    detached input, so that their gradient reaches the weights and not the input; None when mem_len == 0); rk [P, n, d]: the
+    projected position table, row p = relative position p; r_w_bias, r_r_bias [n, d].  The queries of segment s (seg_len rows) attend
+    the rows [s seg_len - mlen, (s + 1) seg_len), mlen = min(mem_len, s seg_len), the first mlen of them through k_mem / v_mem:
+
+        score = scale ((q + r_w_bias) K^T + rel_shift((q + r_r_bias) rk[klen - 1 .. 0]^T)),   out = softmax(score) V
+
+    with the reference's pad-and-view rel_shift and NO mask (the wrapped entries take part).  Gradients reach every tensor argument.
+    The kernels where txl_attention_supported holds, else txl_attention_composed."""
+    seg_len, mem_len = int(seg_len), int(mem_len)
+    if not txl_attention_supported(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len, mem_len):
+        return launch_tagged("txl_composed", lambda: txl_attention_composed(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len,
+                                                                             mem_len, scale))
+    return _TxlAttnFn.apply(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len, mem_len, float(scale))

@@ -16,3 +16,4 @@ from .hgt import HGT, DecompMultiTransform, HeteroGraphTransLayer  # noqa: F401
 from .edge_seq import EdgeSeqModel  # noqa: F401
 from .cnn import CNN, CNNLayer  # noqa: F401
 from .rnn import RNN, RNNLayer  # noqa: F401
+from .txl import TXLFF, MixtureDict, TransformerXL, TXLAttn, TXLLayer  # noqa: F401

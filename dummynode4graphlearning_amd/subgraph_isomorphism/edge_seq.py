@@ -1,4 +1,4 @@
-"""EdgeSeqModel: the shared part of the SI count models on edge sequences (CNN in cnn.py, RNN in rnn.py; TransformerXL can follow on it).
+"""EdgeSeqModel: the shared part of the SI count models on edge sequences (CNN in cnn.py, RNN in rnn.py, TransformerXL in txl.py).
 
 Same constructor keys, state_dict names / shapes, RNG order, forward(pattern, graph) -> OutputDict (p_e_emb, g_e_emb, p_e_rep,
 g_e_rep, p_e_mask, g_e_mask, pred_c, pred_e) and expand(**kw) as subgraph_isomorphism/models/basemodel.py:222-626.  pattern / graph
@@ -8,7 +8,7 @@ the forward are its own.  All tensors stay in rows layout [B, L, C].
 
 Two paths behind `with ops.eseq_fused(on)` (default ops.ESEQ_FUSED_DEFAULT): composed = the reference's arithmetic in torch ops (CPU
 tensors too, and every case the kernels refuse); fused = dn_eseq.hip (filter gate, the CNN layers) / dn_eseq_rnn.hip (the RNN layers,
-whose own default is ops.ESEQ_RNN_FUSED_DEFAULT) + ops.si_embed.
+whose own default is ops.ESEQ_RNN_FUSED_DEFAULT) / dn_txl.hip (the TXL layers, ops.TXL_FUSED_DEFAULT) + ops.si_embed.
 
 Quirks of the reference kept: ScalarFilter compares against the pattern's PADDED zeros too (label 0 passes for every pattern shorter
 than the longest of the batch); a sequence of length 0 gets an all-ones mask (batch_convert_len_to_mask's `mask[i, :-0]`); the

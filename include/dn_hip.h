@@ -1350,6 +1350,32 @@ int dn_eseq_rnn_fwd_f32(int64_t B, int32_t L, int32_t Hd, int32_t D, int32_t cel
 int dn_eseq_rnn_bwd_f32(int64_t B, int32_t L, int32_t Hd, int32_t D, int32_t cell, const float* dy, const float* gate, const int32_t* lo,
                         const float* whh, const float* h, const float* saved, float* dP, float* dhn, dn_stream_t stream);
 
+/* ---- The TransformerXL count model's attention (csrc/dn_txl.hip): relative-position attention over a sliding memory as a banded
+ *   attention over the whole padded sequence, rows layout, fp32.
+ *   q, k, v, k_mem, v_mem, out, dout [B, Lp, n, D]; rk [P, n, D] indexed by relative position; r_w_bias, r_r_bias [n, D]; stats
+ *   [B, Lp, n, 2] (row max, log of the sum).  D in {16, 32, 64}; seg in {16, 32, 48, 64}; mem a multiple of 16 with seg + mem <= 128;
+ *   Lp a multiple of seg; P >= seg + mem; B Lp n D and B (Lp / seg) n P D below 2^31.  The queries of segment s attend the rows
+ *   [s seg - mlen, (s + 1) seg), mlen = min(mem, s seg): the first mlen of them are read from k_mem / v_mem, the others from k / v
+ *   (mem == 0: k_mem / v_mem may be NULL).  score = scale ((q + r_w_bias) K^T + rel_shift((q + r_r_bias) rk^T)) with the reference's
+ *   pad-and-view shift; softmax over the whole window.
+ *   dn_txl_attn_fwd_f32   out and stats, ONE launch.
+ *   dn_txl_attn_bwd_f32   dq_ac / dq_bd [B, Lp, n, D]: the gradient at q through the AC and through the BD term (their sums over
+ *                         (b, row) are the gradients at r_w_bias / r_r_bias); dk, dv: the gradient at the own rows; k_part, v_part
+ *                         [B, S, n, mem, D]: at each window's memory rows; rk_part [B, S, n, P, D]: at rk's rows 0 .. klen - 1.
+ *   dn_txl_fold_mem_f32   dk_mem, dv_mem [B, Lp, n, D] = k_part / v_part summed per row in segment order.
+ *   dn_txl_reduce_rk_f32  drk [P, n, D] = rk_part summed over (sequence, segment) in a fixed order.  No atomics anywhere. */
+int dn_txl_attn_fwd_f32(int64_t B, int32_t Lp, int32_t n, int32_t D, int32_t seg, int32_t mem, int32_t P, float scale, const float* q,
+                        const float* k, const float* v, const float* k_mem, const float* v_mem, const float* rk, const float* r_w_bias,
+                        const float* r_r_bias, float* out, float* stats, dn_stream_t stream);
+int dn_txl_attn_bwd_f32(int64_t B, int32_t Lp, int32_t n, int32_t D, int32_t seg, int32_t mem, int32_t P, float scale, const float* dout,
+                        const float* q, const float* k, const float* v, const float* k_mem, const float* v_mem, const float* rk,
+                        const float* r_w_bias, const float* r_r_bias, const float* out, const float* stats, float* dq_ac, float* dq_bd,
+                        float* dk, float* dv, float* k_part, float* v_part, float* rk_part, dn_stream_t stream);
+int dn_txl_fold_mem_f32(int64_t B, int32_t Lp, int32_t n, int32_t D, int32_t seg, int32_t mem, const float* k_part, const float* v_part,
+                        float* dk_mem, float* dv_mem, dn_stream_t stream);
+int dn_txl_reduce_rk_f32(int64_t B, int32_t Lp, int32_t n, int32_t D, int32_t seg, int32_t mem, int32_t P, const float* rk_part, float* drk,
+                         dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
