@@ -14,6 +14,7 @@ _GRAPH_KERNELS = ("GraphKernelData", "wl_colors", "wl_features", "wl_gram_matric
 _GRAPH_KERNELS_SPGR = ("sp_features", "gr_features", "sp_gram_matrix", "gr_gram_matrix")
 _GRAPH_KERNELS_KWL = ("kwl_colors", "kwl_features", "kwl_gram_matrices")
 _GRAPH_KERNELS_K3WL = ("k3wl_colors", "k3wl_features", "k3wl_gram_matrices")
+_GRAPH_KERNELS_SVM = ("read_gram", "normalize_gram_svm", "split_indices", "kernel_svm_evaluation", "evaluate_dataset", "format_table")
 
 
 def __getattr__(name):
@@ -35,4 +36,8 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(".graph_kernels_k3wl", __name__)
         return mod if name == "graph_kernels_k3wl" else getattr(mod, name)
+    if name == "graph_kernels_svm" or name in _GRAPH_KERNELS_SVM:                  # (a command line too)
+        import importlib
+        mod = importlib.import_module(".graph_kernels_svm", __name__)
+        return mod if name == "graph_kernels_svm" else getattr(mod, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

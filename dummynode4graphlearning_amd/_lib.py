@@ -236,6 +236,8 @@ _SIGS = {
     "dn_txl_attn_bwd_f32": (ctypes.c_int, [c_i64] + [c_i32] * 6 + [c_f32] + [P] * 18 + [P]),
     "dn_txl_fold_mem_f32": (ctypes.c_int, [c_i64] + [c_i32] * 5 + [P] * 4 + [P]),
     "dn_txl_reduce_rk_f32": (ctypes.c_int, [c_i64] + [c_i32] * 6 + [P] * 2 + [P]),
+    "dn_svm_max_rows": (c_i32, []),
+    "dn_svm_smo_f64": (ctypes.c_int, [c_i64, c_i64, P, c_i64, P, c_i64, P, c_i64, P, c_i32, ctypes.c_double, c_i32] + [P] * 5 + [P]),
 }
 
 _lib = None

@@ -5979,3 +5979,220 @@ def txl_attention(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len, mem_le
         return launch_tagged("txl_composed", lambda: txl_attention_composed(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len,
                                                                              mem_len, scale))
     return _TxlAttnFn.apply(q, k, v, k_mem, v_mem, rk, r_w_bias, r_r_bias, seg_len, mem_len, float(scale))
+
+
+# ------------------------------------------------------------------------------------------------ kernel-SVM evaluation: batched SMO
+# (dn_svm.hip; the evaluation -- reader, splits, one-vs-one votes, tables, command line -- is graph_kernels_svm.py)
+# The default of graph_kernels_svm.evaluate_dataset, and the iterations a launch of dn_svm_smo_f64 may run per solve: both measured by
+# tools/graph_kernel_svm_bench.py (docs/LAB_NOTES.md "Graph kernels: SVM evaluation"; 4110 NCI1-shaped graphs, WL at H = 5, 3288 training
+# rows).  On the subset the composed path can finish (1 seed x 6 matrices x C in {1, 0.1, 0.01, 0.001}: 24 duals, 39,537 iterations)
+# fused and composed alternated in one process took 0.040 against 1.91 s, every fused round faster than every composed round, so the
+# kernel is the default.  The whole search (420 duals, 8.68 M iterations) took 8.7 s in 44 launches of at most 20,000 iterations, the
+# longest 284 ms; at 5,000 it took 8.7 s in 173 launches, the longest 112 ms: far below a second at no cost, so that is the default.
+SVM_FUSED_DEFAULT = True
+SVM_ITERS_PER_LAUNCH = 5000
+SVM_TAU = 1e-12
+SVM_CONVERGED, SVM_RUNNING, SVM_CAPPED, SVM_BAD_ROW = 0, 1, 2, 3
+
+
+def svm_fused_enabled():
+    return svm_fused.override(SVM_FUSED_DEFAULT)
+
+
+class svm_fused(_ThreadSwitch):
+    """Context manager: SVM evaluations started inside it (on this thread) solve with dn_svm_smo_f64 (on=True; a solve with more than
+    svm_max_rows() training rows, or on CPU tensors, takes the composed path either way) or with svm_smo_composed (on=False)."""
+    _slot = "svm_fused"
+
+
+def svm_max_rows():
+    """The longest training-row list the SMO kernel keeps in LDS (28 bytes a row)."""
+    return int(lib().dn_svm_max_rows())
+
+
+def svm_smo_supported(K, max_len):
+    """Whether svm_smo takes these solves: a device tensor and no row list above svm_max_rows() rows (its state lives in LDS)."""
+    return bool(K.is_cuda) and int(max_len) <= svm_max_rows()
+
+
+def _svm_table(K, table, rows):
+    """The host's view of a solve table, checked: (matrix, offset, length, positives, C) numpy arrays.  ValueError on anything a
+    kernel could read out of bounds through (the kernel checks again and reports status 3)."""
+    if K.dim() != 3 or K.shape[1] != K.shape[2] or K.dtype != torch.float64:
+        raise ValueError("K must be [num_matrices, n, n] float64 (got %s %s)" % (tuple(K.shape), K.dtype))
+    if table.dim() != 2 or table.shape[1] != 5 or table.dtype != torch.float64 or table.shape[0] < 1:
+        raise ValueError("table must be [num_solves >= 1, 5] float64 {matrix, offset, length, positives, C}")
+    if rows.dim() != 1 or rows.dtype != I32 or rows.numel() < 1:
+        raise ValueError("rows must be a non-empty int32 vector")
+    t = table.detach().cpu().numpy()
+    if not _np.isfinite(t).all() or (t[:, :4] != _np.floor(t[:, :4])).any():
+        raise ValueError("table: matrix, offset, length and positives must be integers, C finite")
+    mat, off, length, npos = (t[:, c].astype(_np.int64) for c in range(4))
+    C = t[:, 4].copy()
+    R, M, n = int(rows.numel()), int(K.shape[0]), int(K.shape[1])
+    if (mat < 0).any() or (mat >= M).any() or (off < 0).any() or (length < 1).any() or (off + length > R).any() or (npos < 0).any() or \
+            (npos > length).any() or not (C > 0).all():
+        raise ValueError("table: a solve names a matrix outside 0..%d, rows outside 0..%d, more positives than rows or C <= 0" % (M - 1, R - 1))
+    if bool(((rows < 0) | (rows >= n)).any()):
+        raise ValueError("rows: an index outside 0..%d" % (n - 1))
+    return mat, off, length, npos, C
+
+
+def _svm_warn_capped(status):
+    if bool((status == SVM_CAPPED).any()):
+        import warnings
+        warnings.warn("WARNING: reaching max number of iterations")
+
+
+def svm_smo(K, table, rows, eps, iters_per_launch=None):
+    """Every C-SVC dual of `table` by SMO, one workgroup per solve (dn_svm_smo_f64): K [M, n, n] float64, table [S, 5] float64
+    {matrix, offset, length, positives, C}, rows int32 (solve s trains on rows[offset .. offset + length), the first `positives` of
+    them its +1 class; the lists of two solves must not overlap: alpha lives at the same offsets).  Returns (alpha [len(rows)], rho [S],
+    iterations [S] int64, status [S] int32).  A launch runs at most iters_per_launch iterations per solve; the solves still running
+    are listed and launched again (one count read back per launch) until none run or libsvm's cap max(10^7, 100 l) stops them
+    (status 2, a warning in libsvm's words, the solve is used as it stands).  The result does not depend on iters_per_launch."""
+    require_gpu(K, table, rows)
+    mat, off, length, npos, C = _svm_table(K, table, rows)
+    if not eps > 0:
+        raise ValueError("eps must be > 0 (got %r)" % (eps,))
+    ipl = SVM_ITERS_PER_LAUNCH if iters_per_launch is None else int(iters_per_launch)
+    if ipl < 1:
+        raise ValueError("iters_per_launch must be >= 1 (got %d)" % ipl)
+    max_len = int(length.max())
+    if max_len > svm_max_rows():
+        raise _lib.DnHipError("svm_smo: a solve with %d training rows exceeds the kernel's %d (svm_smo_supported; svm_smo_composed has "
+                              "no limit)" % (max_len, svm_max_rows()))
+    S, R, dev = int(table.shape[0]), int(rows.numel()), K.device
+    alpha = torch.zeros(R, dtype=torch.float64, device=dev)
+    grad = torch.full((R,), -1.0, dtype=torch.float64, device=dev)
+    rho = torch.zeros(S, dtype=torch.float64, device=dev)
+    iterations = torch.zeros(S, dtype=torch.int64, device=dev)
+    status = torch.full((S,), SVM_RUNNING, dtype=I32, device=dev)
+    todo = None
+    launches_left = S * (int(max(10 ** 7, 100 * max_len)) // ipl + 2)         # (every launch ends or advances a solve: a plain bound)
+    while launches_left > 0:
+        n_list = S if todo is None else int(todo.numel())
+
+        def _launch():
+            check(lib().dn_svm_smo_f64(int(K.shape[0]), int(K.shape[1]), ptr(K), S, ptr(table), n_list, ptr(todo), R, ptr(rows), max_len,
+                                       float(eps), ipl, ptr(alpha), ptr(grad), ptr(rho), ptr(iterations), ptr(status), stream_ptr()),
+                  "dn_svm_smo_f64")
+        launch_tagged("svm_smo", _launch)
+        launches_left -= 1
+        todo = torch.nonzero(status == SVM_RUNNING).view(-1).to(I32)          # (the read-back: how many still run)
+        if todo.numel() == 0:
+            break
+    if bool((status == SVM_BAD_ROW).any()):
+        raise _lib.DnHipError("dn_svm_smo_f64 refused a table row (status 3)")
+    _svm_warn_capped(status)
+    return alpha, rho, iterations, status
+
+
+def svm_smo_composed(K, table, rows, eps, iters_per_launch=None):
+    """svm_smo's algorithm in torch ops, every solve of the table side by side as rows of padded [S, longest list] tensors: any
+    size, any device, CPU tensors too.  The same selection rule, ties, update, clipping, stopping rule, cap and rho; the sums run in
+    torch's order, so the last bits may differ from the kernel's.  iters_per_launch is accepted and ignored (nothing is sliced)."""
+    mat, off, length, npos, C = _svm_table(K, table, rows)
+    if not eps > 0:
+        raise ValueError("eps must be > 0 (got %r)" % (eps,))
+    dev, f64 = K.device, torch.float64
+    S, L, n = len(mat), int(length.max()), int(K.shape[1])
+    ar = _np.arange(L)[None, :]
+    valid_h = ar < length[:, None]
+    slot_h = _np.where(valid_h, off[:, None] + ar, 0)
+    to = lambda a, dt: torch.from_numpy(_np.ascontiguousarray(a)).to(device=dev, dtype=dt)  # noqa: E731
+    valid, slot = to(valid_h, torch.bool), to(slot_h, torch.int64)
+    idx = torch.where(valid, rows.long()[slot], torch.zeros_like(slot))
+    y = to(_np.where(ar < npos[:, None], 1.0, -1.0), f64)
+    Cs = to(C[:, None], f64)
+    base = to(mat[:, None] * n * n, torch.int64)
+    cap = to(_np.maximum(10 ** 7, 100 * length), torch.int64)
+    Kf = K.reshape(-1)
+    diag = Kf[base + idx * (n + 1)]
+    ninf = torch.full((), float("-inf"), dtype=f64, device=dev)
+    a = torch.zeros((S, L), dtype=f64, device=dev)
+    G = torch.full((S, L), -1.0, dtype=f64, device=dev)
+    iters = torch.zeros(S, dtype=torch.int64, device=dev)
+    done = torch.zeros(S, dtype=torch.bool, device=dev)
+    capped = torch.zeros(S, dtype=torch.bool, device=dev)
+    ypos = y > 0
+    check_every = 16 if K.is_cuda else 1
+
+    def first_max(x):                     # (torch.max over a dim returns the index of the FIRST maximal value: the lowest index wins a tie)
+        return x.max(1, keepdim=True)
+
+    def loop(a, G):
+        step = 0
+        while True:
+            v = -y * G
+            up = valid & torch.where(ypos, a < Cs, a > 0)
+            low = valid & torch.where(ypos, a > 0, a < Cs)
+            gmax, i = first_max(torch.where(up, v, ninf))
+            m2 = torch.where(low, -v, ninf).max(1, keepdim=True)[0]
+            Ki = Kf[base + idx.gather(1, i) * n + idx]
+            Kii = diag.gather(1, i)
+            b = gmax - v
+            q = Kii + diag - 2.0 * Ki
+            score, j = first_max(torch.where(low & (b > 0), (b * b) / q.masked_fill(~(q > 0), SVM_TAU), ninf))
+            stop = (~(gmax + m2 >= eps) | (score == ninf)).view(-1)                # (gmax = -inf: no i at all)
+            capped.logical_or_(~done & (iters >= cap))                                       # (libsvm leaves its loop at the cap without a look at the rule)
+            done.logical_or_(stop | capped)
+            frozen = done.view(-1, 1)
+            Kj = Kf[base + idx.gather(1, j) * n + idx]
+            yi, yj, Gi, Gj, oai, oaj = y.gather(1, i), y.gather(1, j), G.gather(1, i), G.gather(1, j), a.gather(1, i), a.gather(1, j)
+            Qij = yi * yj * Ki.gather(1, j)
+            Kjj = diag.gather(1, j)
+            # y_i != y_j
+            qd = Kii + Kjj + 2.0 * Qij
+            qd = qd.masked_fill(qd <= 0, SVM_TAU)
+            delta = (-Gi - Gj) / qd
+            diff = oai - oaj
+            ai, aj = oai + delta, oaj + delta
+            c1 = (diff > 0) & (aj < 0)
+            c2 = ~(diff > 0) & (ai < 0)
+            ai, aj = torch.where(c1, diff, ai.masked_fill(c2, 0.0)), torch.where(c2, -diff, aj).masked_fill(c1, 0.0)
+            c1 = (diff > 0) & (ai > Cs)
+            c2 = ~(diff > 0) & (aj > Cs)
+            ai_d, aj_d = torch.where(c1, Cs, torch.where(c2, Cs + diff, ai)), torch.where(c1, Cs - diff, torch.where(c2, Cs, aj))
+            # y_i == y_j
+            qs = Kii + Kjj - 2.0 * Qij
+            qs = qs.masked_fill(qs <= 0, SVM_TAU)
+            delta = (Gi - Gj) / qs
+            tot = oai + oaj
+            ai, aj = oai - delta, oaj + delta
+            c1 = (tot > Cs) & (ai > Cs)
+            c2 = ~(tot > Cs) & (aj < 0)
+            ai, aj = torch.where(c1, Cs, torch.where(c2, tot, ai)), torch.where(c1, tot - Cs, aj.masked_fill(c2, 0.0))
+            c1 = (tot > Cs) & (aj > Cs)
+            c2 = ~(tot > Cs) & (ai < 0)
+            ai_s, aj_s = torch.where(c1, tot - Cs, ai.masked_fill(c2, 0.0)), torch.where(c1, Cs, torch.where(c2, tot, aj))
+            same = yi == yj
+            ai = torch.where(frozen, oai, torch.where(same, ai_s, ai_d))
+            aj = torch.where(frozen, oaj, torch.where(same, aj_s, aj_d))
+            G = G + ((y * yi * Ki) * (ai - oai) + (y * yj * Kj) * (aj - oaj))     # (libsvm's association: symmetric problems stay symmetric)
+            a = a.scatter(1, i, ai).scatter(1, j, aj)
+            iters.add_((~done).to(torch.int64))
+            step += 1
+            if step % check_every == 0 and bool(done.all()):
+                return a, G
+
+    threads = torch.get_num_threads()
+    if not K.is_cuda:                      # (a step is some sixty ops on small [S, L] tensors: waking a thread pool for each costs more
+        torch.set_num_threads(1)           #  than it computes)
+    try:
+        a, G = loop(a, G)
+    finally:
+        torch.set_num_threads(threads)
+    status = torch.where(capped, torch.full_like(iters, SVM_CAPPED), torch.full_like(iters, SVM_CONVERGED)).to(I32)
+    yG = y * G
+    free = valid & (a > 0) & (a < Cs)
+    at_c, at_0 = valid & (a >= Cs), valid & (a <= 0)
+    inf = torch.full((), float("inf"), dtype=f64, device=dev)
+    ub = torch.where((at_c & ~ypos) | (at_0 & ypos), yG, inf).min(1)[0]
+    lb = torch.where((at_c & ypos) | (at_0 & ~ypos), yG, ninf).max(1)[0]
+    nfree = free.sum(1)
+    rho = torch.where(nfree > 0, torch.where(free, yG, torch.zeros_like(yG)).sum(1) / nfree.clamp(min=1), (ub + lb) / 2.0)
+    alpha = torch.zeros(int(rows.numel()), dtype=f64, device=dev)
+    alpha[slot[valid]] = a[valid]
+    _svm_warn_capped(status)
+    return alpha, rho, iters, status

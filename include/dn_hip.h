@@ -1376,6 +1376,25 @@ int dn_txl_fold_mem_f32(int64_t B, int32_t Lp, int32_t n, int32_t D, int32_t seg
 int dn_txl_reduce_rk_f32(int64_t B, int32_t Lp, int32_t n, int32_t D, int32_t seg, int32_t mem, int32_t P, const float* rk_part, float* drk,
                          dn_stream_t stream);
 
+/* ---- kernel-SVM evaluation of gram matrices: batched SMO for the C-SVC dual on precomputed kernels (dn_svm.hip) ----
+ * The counterpart of scikit-learn's SVC(kernel="precomputed") inside graph_classification/graph_kernels/seed_svm.py, in fp64:
+ * minimise 1/2 a^T Q a - sum(a), 0 <= a <= C, y^T a = 0, Q_tu = y_t y_u K_tu, with libsvm's second-order working-set selection
+ * (ties to the lowest index, TAU = 1e-12), its update and clipping, its stopping rule m - M < eps and its rho; no shrinking.
+ *   K      [num_matrices, n, n] doubles; the kernel rows of a solve are gathered out of it, nothing is copied per solve.
+ *   table  [num_solves, 5] doubles {matrix, offset, length, positives, C}: the solve's training rows are rows[offset .. offset +
+ *          length) (row indices into its matrix), the first `positives` of them the +1 class.
+ *   list   the solves of this launch (NULL: all of them, num_list == num_solves); one workgroup each.
+ *   alpha, grad [num_rows] doubles at the offsets of `rows`: the state, read at the start of a launch and stored at its end (a
+ *          fresh solve starts from alpha = 0, grad = -1, iterations = 0); rho [num_solves]; iterations [num_solves] (int64).
+ *   status [num_solves]: 0 converged, 1 still running after iters_per_launch more iterations, 2 libsvm's cap max(10^7, 100 length)
+ *          reached, 3 the table row or a row index is out of range (nothing is computed for that solve).
+ * max_len = the longest row list of the table (the launch's LDS: 28 bytes a row), at most dn_svm_max_rows(); a longer list in the
+ * table gets status 3.  No atomics, fixed reduction order: the result does not depend on iters_per_launch, two runs give the same bits. */
+int32_t dn_svm_max_rows(void);
+int dn_svm_smo_f64(int64_t num_matrices, int64_t n, const double* K, int64_t num_solves, const double* table, int64_t num_list,
+                   const int32_t* list, int64_t num_rows, const int32_t* rows, int32_t max_len, double eps, int32_t iters_per_launch,
+                   double* alpha, double* grad, double* rho, int64_t* iterations, int32_t* status, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
