@@ -147,9 +147,29 @@ __global__ __launch_bounds__(kThreads) void rows_chain2_ring_kernel(
     // ---- DMA side: rows 4 w .. 4 w + 3 of a tile are this wave's (two wave-instructions of 2 rows)
     const int rin = lane >> 5, pos = lane & 31;
     const char* zero = reinterpret_cast<const char*>(g_c2_zero);
+    // A tile wholly below N is 32 consecutive rows: one wave-uniform 64-bit base (scalar arithmetic) + a lane offset that never
+    // changes (the second pair of rows: (r + 2) & 15 = (r & 15) ^ 2, the same offset XOR 32); the last partial tile and the
+    // run-ahead tiles take the per-lane path.  Both issue the same vector-memory operations in the same order (c2_wait counts them).
+    static_assert(kDma == 2, "the scalar-base path spells out a wave's two row DMAs");
+    const int nfull = N / kTR;
+    unsigned dma_off = (unsigned)(rin * kRowB + ((pos ^ ((4 * wave + rin) & 15)) << 4));
+    asm volatile("" : "+v"(dma_off));
     auto issue = [&](int T) __attribute__((always_inline)) {
         const unsigned st = lds_base + (unsigned)(T % kNS) * kStageB;
         const int64_t rb = rowbase(T);
+        if (first + T * step < nfull) {
+            const uint64_t xb = (uint64_t)(uintptr_t)X + (uint64_t)(rb + 4 * wave) * kRowB;
+            const unsigned sw = st + (unsigned)(4 * wave) * kRowB;
+            glds16_s(xb, dma_off, sw);
+            glds16_s(xb + 2 * kRowB, dma_off ^ 32u, sw + 2 * kRowB);
+            if constexpr (KEEP) {
+                const uint64_t boff = (uint64_t)rb * (kH / 8);
+                const unsigned lo = (unsigned)lane << 4;
+                if (wave == (T & 7)) glds16_s((uint64_t)(uintptr_t)mask0 + boff, lo, st + kTileB);
+                if (wave == ((T + 4) & 7)) glds16_s((uint64_t)(uintptr_t)mask1 + boff, lo, st + kTileB + kBitsB);
+            }
+            return;
+        }
 #pragma unroll
         for (int jj = 0; jj < kDma; ++jj) {
             const int rl = 4 * wave + 2 * jj + rin;                       // row of the tile this lane fills

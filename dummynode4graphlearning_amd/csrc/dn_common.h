@@ -92,6 +92,17 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
                  : "memory");
 }
 
+// ... from a wave-uniform 64-bit base in SGPRs + a 32-bit unsigned byte offset per lane (the scalar-base form of the same
+// instruction): a tile of consecutive rows costs the lanes no 64-bit address arithmetic.  The s_nop also covers a base that a
+// v_readfirstlane has just written (5 wait states before a vector-memory instruction reads such an SGPR).
+__device__ __forceinline__ void glds16_s(uint64_t base, unsigned lane_off, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 2\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(lane_off), "s"(base), "s"(lds_dst)
+                 : "memory");
+}
+
 __device__ __forceinline__ void glds4(const void* gsrc, unsigned lds_dst) {      // 4 bytes per lane: lane l lands at lds_dst + 4 l
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"

@@ -12,7 +12,7 @@
 // partition, the input gradient's eight k-steps in order from a zero accumulator, the mask applied to the fp32 sums before the
 // one rounding to bf16 -- all five results are bit-identical to rows_wgrad_dma_kernel / rows_wgrad_ls_kernel + rows_chain2_ring_kernel.
 //
-// One workgroup per chunk (and per CU: 136 KiB of LDS), 8 self-loading waves at 2 per SIMD (256 registers a wave):
+// One workgroup per chunk (and per CU: 136 KiB of LDS, + a 4 KiB table with masks), 8 self-loading waves at 2 per SIMD (256 registers a wave):
 //   * a wave keeps its 128 x 64 part of the weight gradient (128 registers, as in the weight-gradient kernels) AND the weight's
 //     32 output columns for the input gradient (64 registers, the ring transform's column order) + 8 for that product's sums,
 //     taken one 16-row half of the tile at a time (with both halves' sums and fragments live the allocator spilled);
@@ -27,7 +27,13 @@
 //   * fragment reads are inline asm with hand-counted lgkmcnt waits (dn_rel_ring.hip): the weight gradient's G fragments run
 //     two ahead of their MFMAs, the input gradient keeps four k-steps' fragments in flight;
 //   * the input-gradient rows leave straight from the accumulators, 16 bytes per lane and row (rows past the chunk's end go to
-//     a dump area so that every wave issues the same vector-memory operations per tile: the DMA waits are counted).
+//     a dump area so that every wave issues the same vector-memory operations per tile: the DMA waits are counted);
+//   * the lanes do no 64-bit address arithmetic for a tile wholly inside the chunk: its row DMAs take a wave-uniform base from
+//     scalar registers + a constant 32-bit lane offset (glds16_s), its result rows a uniform base + a constant lane offset; only
+//     the chunk's last partial tile and the run-ahead tiles behind it take the per-lane path (a wave-uniform branch);
+//   * a mask byte becomes the keep mask of its 8 bf16 by ONE ds_read_b128 from a 256-entry table built at kernel start (slope 0:
+//     one AND per packed pair, in the input gradient after the rounding -- keep-or-zero commutes with it; slope != 0: the
+//     bit-select on the mask pass, the fp32 blend from bit-field extracts on the input gradient).  docs/LAB_NOTES.md, round 9.
 // No workgroup waits on another.
 #include "dn_common.h"
 #include "dn_internal.h"
@@ -42,6 +48,7 @@ constexpr int kMatB = kTR * kRowB;             // 16 KiB: one operand's tile
 constexpr int kBitsB = kTR * (kH / 8);         // 1 KiB: one tile of mask bits
 constexpr int kStB = 2 * kMatB + 2 * kBitsB;   // a stage: G rows, A rows, mask_in bits, mask_out bits
 constexpr int kNST = 4;                        // ring stages (136 KiB)
+constexpr int kTabB = 256 * 16;                // behind the ring: mask byte -> keep mask of its 8 bf16 (4 words), 4 KiB
 constexpr int kThreads = 512;
 constexpr int kDma = 4, kST = 2;               // per wave and tile: 4 row DMAs (+ a tile's bits on one wave), then 2 result stores
 static_assert(kStB % 1024 == 0, "the fragment addressing XORs low bits of stage-relative offsets");
@@ -93,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
                                                                  const Chunk* __restrict__ chunks, float* __restrict__ partial,
                                                                  float* __restrict__ colsum_partial, bf16_t* __restrict__ Gn,
                                                                  float slope) {
-    __shared__ __attribute__((aligned(1024))) char lds[kNST * kStB];
+    __shared__ __attribute__((aligned(1024))) char lds[kNST * kStB + (MASKED ? kTabB : 0)];
     const unsigned lds_base = lds_addr(lds);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -111,6 +118,16 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
     bf16x8 wf[8][2];
     dn_load_w_kn32<8>(Wkn, kH, 32 * wave, lane, lds + wave * 2048, wf);  // (wave-private scratch inside the idle ring)
     wait_vmcnt<0>();                                                      // no ordinary load may be pending once the DMAs start
+    if constexpr (MASKED) {
+        // the keep-mask table: word i of entry b = 0xffff where bit 2 i of b is set | 0xffff0000 where bit 2 i + 1 is (the two
+        // bf16 of a packed pair); a mask byte costs one ds_read_b128 instead of eight bit-field extracts and twelve logic ops
+        if (tid < 256) {
+            u32x4 e;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) e[i] = ((tid >> (2 * i)) & 1 ? 0xffffu : 0u) | ((tid >> (2 * i + 1)) & 1 ? 0xffff0000u : 0u);
+            *reinterpret_cast<u32x4*>(lds + kNST * kStB + tid * 16) = e;
+        }
+    }
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
@@ -118,18 +135,43 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
     __syncthreads();                                                      // every wave is done with its scratch: the ring may fill
 
     // ---- DMA side: rows 4 w .. 4 w + 3 of both operands of a tile are this wave's (two wave-instructions of 2 rows each)
-    // (Every phase of the loop derives its lane-dependent addresses anew from `fresh()`: hoisted out of the loop they would be ~40
-    //  more registers live across it, and the accumulators + weights leave 48.)
+    // (The accumulators + weights leave 48 registers.  Four 32-bit lane constants live across the loop -- dma_off, mask_byte, off0,
+    //  st_off, each pinned by an empty asm; the fragment addresses of the weight gradient and everything the partial-tile path
+    //  needs are derived anew from `fresh()` in their phase: hoisted they would be ~40 more registers live across the loop.)
     auto fresh = [&]() __attribute__((always_inline)) {
         int l = lane;
         asm volatile("" : "+v"(l));
         return l;
     };
     const char* zero = reinterpret_cast<const char*>(g_mb_zero);
+    // A tile wholly inside the chunk is 32 consecutive rows: its source is ONE wave-uniform 64-bit base (in SGPRs, from scalar
+    // arithmetic) + a lane offset that never changes -- row-in-pair x 512 + the swizzled piece (the second pair of rows: s(r + 2) =
+    // s(r) ^ 4, the same offset XOR 64); 16 x lane for a tile of bits.  One register lives across the loop instead of five 64-bit
+    // addresses worked out per tile.  The chunk's last partial tile and the run-ahead tiles behind it take the per-lane path below
+    // (a wave-uniform branch); both paths issue the same vector-memory operations in the same order -- mb_wait counts them.
+    const int nfull = (cend - cbeg) / kTR;                                // tiles wholly inside the chunk (32-bit: a scalar compare)
+    unsigned dma_off = (unsigned)((lane >> 5) * kRowB + (((lane & 31) ^ swz(4 * wave + (lane >> 5))) << 4));
+    asm volatile("" : "+v"(dma_off));
     auto issue = [&](int T) __attribute__((always_inline)) {
-        const int ln = fresh(), rin = ln >> 5, cpos = ln & 31;
         const unsigned st = lds_base + (unsigned)(T % kNST) * kStB;
         const int64_t r0 = (int64_t)cbeg + (int64_t)T * kTR;
+        if (T < nfull) {
+            const uint64_t rowoff = (uint64_t)(r0 + 4 * wave) * kRowB;
+            const uint64_t gb = (uint64_t)(uintptr_t)G + rowoff, ab = (uint64_t)(uintptr_t)A + rowoff;
+            const unsigned off1 = dma_off ^ 64u, sw = st + (unsigned)(4 * wave) * kRowB;
+            glds16_s(gb, dma_off, sw);
+            glds16_s(gb + 2 * kRowB, off1, sw + 2 * kRowB);
+            if constexpr (MASKED) {
+                const uint64_t boff = (uint64_t)r0 * (kH / 8);
+                const unsigned lo = (unsigned)lane << 4;
+                if (wave == (T & 7)) glds16_s((uint64_t)(uintptr_t)bits_in + boff, lo, st + 2 * kMatB);
+                if (wave == ((T + 4) & 7)) glds16_s((uint64_t)(uintptr_t)bits_out + boff, lo, st + 2 * kMatB + kBitsB);
+            }
+            glds16_s(ab, dma_off, sw + (unsigned)kMatB);
+            glds16_s(ab + 2 * kRowB, off1, sw + (unsigned)kMatB + 2 * kRowB);
+            return;
+        }
+        const int ln = fresh(), rin = ln >> 5, cpos = ln & 31;
         uint64_t pas[2];
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
@@ -167,28 +209,43 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
             cs[2 * i + 1] += __uint_as_float(w[i] & 0xffff0000u);
         }
     };
+    unsigned mask_byte = 0;                                               // my byte of a tile's mask_in bits (row mrow; + 512: row mrow + 16)
+    if constexpr (MASKED) {
+        mask_byte = (unsigned)((2 * wave + (lane >> 5)) * (kH / 8) + ((lane & 31) ^ swz(2 * wave + (lane >> 5))));
+        asm volatile("" : "+v"(mask_byte));
+    }
     auto mask_tile = [&](int T) __attribute__((always_inline)) {          // the G rows of tile T in place (+ their column sums)
-        const int ln = fresh(), mrow = 2 * wave + (ln >> 5), mq = ln & 31, mchunk = mq ^ swz(mrow);
+        // (row mrow = 2 wave + (lane >> 5), position lane & 31: byte 1024 wave + 16 lane of the tile; mask_byte: its byte of bits)
         char* sT = lds + (T % kNST) * kStB;
-        const uint8_t* sB = reinterpret_cast<const uint8_t*>(sT + 2 * kMatB);
+        const uint8_t* sB = reinterpret_cast<const uint8_t*>(sT + 2 * kMatB) + mask_byte;
+        const u32x4* tab = reinterpret_cast<const u32x4*>(lds + kNST * kStB);
+        u32x4* pp[2];
+        u32x4 v[2], mk[2];
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
-            const int r = mrow + 16 * jj;
-            u32x4* pp = reinterpret_cast<u32x4*>(sT + r * kRowB + mq * 16);
-            const int32_t kb = (int32_t)sB[r * (kH / 8) + mchunk];
-            u32x4 v = *pp;
-            // keep where the bit is set, x slope (0: zero) elsewhere = dn_keep_or_scale_bits, branch-free: word masks from signed
-            // 1-bit field extracts (0 / ~0) and one bit-select (rows_chain2_ring_kernel's form)
+            pp[jj] = reinterpret_cast<u32x4*>(sT + wave * 1024 + 16 * jj * kRowB + (lane << 4));
+            mk[jj] = tab[sB[16 * jj * (kH / 8)]];
+            v[jj] = *pp[jj];
+        }
+        // keep where the bit is set, x slope (0: zero) elsewhere = dn_keep_or_scale_bits, branch-free: the byte's word masks
+        // from the table and one AND (slope 0) or one bit-select
+        if (slope == 0.f) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe(kb, 2 * i, 1), m1 = (uint32_t)__builtin_amdgcn_sbfe(kb, 2 * i + 1, 1);
-                const uint32_t mk = (m0 & 0xffffu) | (m1 & 0xffff0000u);
-                uint32_t alt = 0u;
-                if (slope != 0.f) alt = pack_bf16x2(__uint_as_float(v[i] << 16) * slope, __uint_as_float(v[i] & 0xffff0000u) * slope);
-                v[i] = (v[i] & mk) | (alt & ~mk);
-            }
-            *pp = v;
-            add_cs(make_uint4(v[0], v[1], v[2], v[3]));
+            for (int jj = 0; jj < 2; ++jj) v[jj] &= mk[jj];
+        } else {
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t alt =
+                        pack_bf16x2(__uint_as_float(v[jj][i] << 16) * slope, __uint_as_float(v[jj][i] & 0xffff0000u) * slope);
+                    v[jj][i] = (v[jj][i] & mk[jj][i]) | (alt & ~mk[jj][i]);
+                }
+        }
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+            *pp[jj] = v[jj];
+            add_cs(make_uint4(v[jj][0], v[jj][1], v[jj][2], v[jj][3]));
         }
     };
     auto colsum_tile = [&](int T) __attribute__((always_inline)) {        // (unmasked: the column sums of tile T as it lies)
@@ -216,6 +273,10 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
     //      (stage + off0) ^ (ks & 3) << 6, + 256 for ks >= 4
     f32x4 dacc[2];
     bf16x8 xf[4];
+    // (lane constants of this phase kept across the loop: the fragment address inside a stage, and my 16 bytes of row j of Gn)
+    unsigned off0 = lds_base + (unsigned)((lane & 15) * kRowB + (((lane >> 4) ^ swz(lane & 15)) << 4));
+    unsigned st_off = (unsigned)((lane & 15) * kRowB + (32 * wave + 8 * (lane >> 4)) * 2);
+    asm volatile("" : "+v"(off0), "+v"(st_off));
 
     // (HH: rows j of the tile's first or second 16 rows -- the sums of one half at a time: 8 registers, 4 per fragment)
 #define DN_MB_FETCH(SLOT, KS, HH)                                                                                     \
@@ -237,38 +298,62 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
     // Gn's sums of one half: eight k-steps in order, four fragments in flight (reads in the queue behind the one a k-step waits
     // for: 3, ..., then 2, 1, 0); then the rows leave straight from the accumulators: mask_out on the fp32 sums (keep where the
     // bit is set, x slope -- 0: zero -- elsewhere, as rows_chain2_ring_kernel's), one rounding to bf16, one 16-byte store
+    // MASKED: the half's byte of mask_out bits is requested AHEAD of the fragments (it has landed with the first of them) and its
+    // table entry behind k-step 0 -- one more read in the queue behind the fragments of k-steps 1-3 (count 4), landed with the
+    // fragment of k-step 4.  Slope 0: keep-or-zero commutes with the one rounding, so the packed pairs are ANDed with the entry.
+#define DN_MB_KSTEP_M(SLOT, KS, CNT_MASKED, CNT_PLAIN)                                                                \
+    if constexpr (MASKED) { DN_MB_KSTEP(SLOT, KS, CNT_MASKED) } else { DN_MB_KSTEP(SLOT, KS, CNT_PLAIN) }
 #define DN_MB_DGRAD_HALF(HH)                                                                                          \
     {                                                                                                                 \
+        uint32_t kb = 0;                                                                                              \
+        u32x4 km = {0u, 0u, 0u, 0u};                                                                                  \
+        if constexpr (MASKED) {                                                                                       \
+            if ((HH) == 0) asm volatile("ds_read_u8 %0, %1" : "=v"(kb) : "v"(bitaddr));                               \
+            else asm volatile("ds_read_u8 %0, %1 offset:512" : "=v"(kb) : "v"(bitaddr));                              \
+        }                                                                                                             \
         DN_MB_FETCH(0, 0, HH) DN_MB_FETCH(1, 1, HH) DN_MB_FETCH(2, 2, HH) DN_MB_FETCH(3, 3, HH)                       \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
-        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(xf[0]));                                                           \
+        if constexpr (MASKED) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(xf[0]), "+v"(kb));                           \
+        else asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(xf[0]));                                                      \
         _Pragma("unroll") for (int n = 0; n < 2; ++n)                                                                  \
             dacc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][n], xf[0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);  \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
+        if constexpr (MASKED) {                                                                                       \
+            const unsigned ta_ = lds_base + (unsigned)(kNST * kStB) + (kb << 4);                                      \
+            DN_DS_READ128(km, ta_, 0);                                                                                \
+        }                                                                                                             \
         DN_MB_FETCH(0, 4, HH) __builtin_amdgcn_sched_barrier(0);                                                      \
-        DN_MB_KSTEP(1, 1, 3) DN_MB_FETCH(1, 5, HH) __builtin_amdgcn_sched_barrier(0);                                 \
-        DN_MB_KSTEP(2, 2, 3) DN_MB_FETCH(2, 6, HH) __builtin_amdgcn_sched_barrier(0);                                 \
-        DN_MB_KSTEP(3, 3, 3) DN_MB_FETCH(3, 7, HH) __builtin_amdgcn_sched_barrier(0);                                 \
+        DN_MB_KSTEP_M(1, 1, 4, 3) DN_MB_FETCH(1, 5, HH) __builtin_amdgcn_sched_barrier(0);                            \
+        DN_MB_KSTEP_M(2, 2, 4, 3) DN_MB_FETCH(2, 6, HH) __builtin_amdgcn_sched_barrier(0);                            \
+        DN_MB_KSTEP_M(3, 3, 4, 3) DN_MB_FETCH(3, 7, HH) __builtin_amdgcn_sched_barrier(0);                            \
         DN_MB_KSTEP(0, 4, 3)                                                                                          \
         DN_MB_KSTEP(1, 5, 2)                                                                                          \
         DN_MB_KSTEP(2, 6, 1)                                                                                          \
         DN_MB_KSTEP(3, 7, 0)                                                                                          \
-        const int64_t p = r0 + 16 * (HH);                                                                             \
+        if constexpr (MASKED) asm volatile("" : "+v"(km));                                                            \
         float v[8];                                                                                                   \
         _Pragma("unroll") for (int n = 0; n < 2; ++n)                                                                  \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) v[4 * n + i] = dacc[n][i];                                       \
-        if constexpr (MASKED) {                                                                                       \
-            const int32_t kb = (int32_t)sB1[(16 * (HH) + j) * (kH / 8) + bcol];                                       \
-            _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                            \
-                const uint32_t mk = (uint32_t)__builtin_amdgcn_sbfe(kb, i, 1);                                        \
-                const uint32_t alt = slope != 0.f ? __float_as_uint(v[i] * slope) : 0u;                               \
-                v[i] = __uint_as_float((__float_as_uint(v[i]) & mk) | (alt & ~mk));                                   \
-            }                                                                                                         \
-        }                                                                                                             \
         u32x4 o;                                                                                                      \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);                      \
-        char* dst = p < (int64_t)cend ? reinterpret_cast<char*>(Gn) + (uint64_t)p * kRowB + ycol : dump;              \
-        __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(dst)); /* (always issued: the DMA waits count it) */  \
+        if (MASKED && slope != 0.f) {                                                                                 \
+            _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                            \
+                const uint32_t mk = (uint32_t)__builtin_amdgcn_sbfe((int32_t)kb, i, 1);                               \
+                v[i] = __uint_as_float((__float_as_uint(v[i]) & mk) | (__float_as_uint(v[i] * slope) & ~mk));         \
+            }                                                                                                         \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);                  \
+        } else {                                                                                                      \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);                  \
+            if constexpr (MASKED) o &= km;                                                                            \
+        }                                                                                                             \
+        /* (a store is always issued: the DMA waits count it) */                                                      \
+        if (full_tile) {                                                                                              \
+            char* dst = reinterpret_cast<char*>(Gn) + (uint64_t)(rt0 + 16 * (HH)) * kRowB + st_off;                   \
+            __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(dst));                                            \
+        } else {                                                                                                      \
+            const int64_t p = rt0 + 16 * (HH) + j;                                                                    \
+            char* dst = p < (int64_t)cend ? reinterpret_cast<char*>(Gn) + (uint64_t)p * kRowB + ycol : dump;          \
+            __builtin_nontemporal_store(o, reinterpret_cast<u32x4*>(dst));                                            \
+        }                                                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
     }
 
@@ -314,13 +399,15 @@ __global__ __launch_bounds__(kThreads) void mlp_bwd_fused_kernel(const bf16_t* _
             }
         }
         {
+            // a tile wholly inside the chunk stores to a uniform base + st_off; the last partial tile per lane, rows past the end
+            // to the dump slot (a wave-uniform branch, one store either way)
             const int ln = fresh(), j = ln & 15, g = ln >> 4;
-            const unsigned off0 = lds_base + (unsigned)(j * kRowB + ((g ^ swz(j)) << 4));
             char* dump = reinterpret_cast<char*>(g_mb_dump) + wave * 1024 + ln * 16;
             const unsigned ycol = (unsigned)(32 * wave + 8 * g) * 2;      // my 16 bytes of a row of Gn
-            const unsigned bcol = (unsigned)(4 * wave + g);               // ... and their byte of mask_out bits
-            const uint8_t* sB1 = reinterpret_cast<const uint8_t*>(lds + (t % kNST) * kStB + 2 * kMatB + kBitsB);
-            const int64_t r0 = (int64_t)cbeg + (int64_t)t * kTR + j;
+            const int64_t rt0 = (int64_t)cbeg + (int64_t)t * kTR;
+            const bool full_tile = t < nfull;
+            // my byte of the tile's mask_out bits: row j (offset 512: row 16 + j), byte 4 wave + g = st_off / 16
+            const unsigned bitaddr = lds_base + sg + (unsigned)(2 * kMatB + kBitsB) + (st_off >> 4);
             DN_MB_DGRAD_HALF(0)
             DN_MB_DGRAD_HALF(1)
         }
