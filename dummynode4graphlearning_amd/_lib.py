@@ -238,6 +238,12 @@ _SIGS = {
     "dn_txl_reduce_rk_f32": (ctypes.c_int, [c_i64] + [c_i32] * 6 + [P] * 2 + [P]),
     "dn_svm_max_rows": (c_i32, []),
     "dn_svm_smo_f64": (ctypes.c_int, [c_i64, c_i64, P, c_i64, P, c_i64, P, c_i64, P, c_i32, ctypes.c_double, c_i32] + [P] * 5 + [P]),
+    "dn_objective_workspace_bytes": (c_sz, [c_i64, c_i32, P]),
+    "dn_objective_fwd": (ctypes.c_int, [c_i64, P, c_i32, P, c_i32] + [c_i64, P, c_i32, P, P, c_i32] * 2 + [c_i32, P, P, P, P, c_i32, c_i32] +
+                         [ctypes.c_double] * 4 + [P, P, P, c_sz, P]),
+    "dn_objective_bwd": (ctypes.c_int, [c_i64, P, P, c_i32, P, c_i32] + [c_i64, P, c_i32, P, P, c_i32] * 2 + [c_i32, P, P, P, P, c_i32] +
+                         [ctypes.c_double] * 4 + [P, P, P, P, P]),
+    "dn_objective_eval": (ctypes.c_int, [c_i64, P, c_i32, P, c_i32] + [c_i64, P, c_i32, P, c_i32] * 2 + [c_i64, c_i64] + [P] * 5 + [P]),
 }
 
 _lib = None

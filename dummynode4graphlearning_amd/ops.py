@@ -6196,3 +6196,240 @@ def svm_smo_composed(K, table, rows, eps, iters_per_launch=None):
     alpha[slot[valid]] = a[valid]
     _svm_warn_capped(status)
     return alpha, rho, iters, status
+
+
+# ------------------------------------------------------------------------------------------------ the SI training objective
+# (dn_objective.hip; the schedules, SIObjective and the epoch meters are subgraph_isomorphism/objective.py)
+# The default of si_objective, by the project's rule: on only if every fused round beats every composed round.  Measured on the scale
+# batch (tools/si_objective_bench.py; docs/LAB_NOTES.md "SI training objective"; 512 pairs, 25,600 graph nodes, H = 64, node weights
+# present, the reference's default schedules, the two paths alternated in one process, 5 rounds): the objective's forward + backward
+# 0.131 ms fused against 0.746 ms composed (6 against 90 device kernels), every fused round faster than every composed round; the RGIN
+# model step 3.76 against 4.07 ms, the fused round faster than the composed round next to it in all five, but the step time drifted
+# from 5.5 to 3.9 ms over the process, so NOT every fused round beat every composed round.  By the rule the kernels stay opt-in:
+# `with ops.objective_fused():`.
+SI_OBJECTIVE_FUSED_DEFAULT = False
+SI_OBJECTIVE_CRITERIA = {"MAE": 0, "MSE": 1, "SMSE": 2}
+SI_OBJECTIVE_TERMS = ("eval", "bp_loss", "match_v_loss", "match_e_loss", "match_v_reg", "match_e_reg", "rep_reg")
+SI_OBJECTIVE_MAX_REPS = 4
+
+
+def objective_fused_enabled():
+    return objective_fused.override(SI_OBJECTIVE_FUSED_DEFAULT)
+
+
+class objective_fused(_ThreadSwitch):
+    """Context manager: si_objective / si_eval_errors calls inside it (on this thread) run dn_objective_* (on=True; anything but
+    fp32 / bf16 CUDA tensors takes the composed path either way) or the torch ops of si_objective_composed (on=False)."""
+    _slot = "objective_fused"
+
+
+def _objective_dt(t):
+    return 0 if t.dtype == torch.float32 else 1
+
+
+def _objective_float(t):
+    return t is None or (t.is_cuda and t.dtype in (torch.float32, torch.bfloat16))
+
+
+def si_objective_supported(pred_c, counts, reps=(), pred_v=None, v_target=None, pred_e=None, e_target=None):
+    """The predicate of the dn_objective_* kernels: fp32 or bf16 CUDA tensors (each its own dtype), at most four representations."""
+    ts = [pred_c, counts, pred_v, v_target, pred_e, e_target] + list(reps)
+    return len(reps) <= SI_OBJECTIVE_MAX_REPS and all(_objective_float(t) for t in ts) and pred_c.numel() >= 1 and \
+        all(r.dim() >= 2 and r.numel() >= 1 for r in reps) and all(t is None or t.numel() >= 1 for t in (pred_v, pred_e))
+
+
+def _objective_crit(name, what):
+    if name not in SI_OBJECTIVE_CRITERIA:
+        raise NotImplementedError("%s %r (MAE, MSE or SMSE)" % (what, name))
+    return SI_OBJECTIVE_CRITERIA[name]
+
+
+class _MaskedZeroPassFn(torch.autograd.Function):
+    """x with its masked entries (mask False) set to 0, the gradient passed through unchanged: what the reference's in-place
+    masked_fill_ under no_grad amounts to (train.py:784), without touching x."""
+
+    @staticmethod
+    def forward(ctx, x, mask):
+        return x.masked_fill(~mask, 0)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def si_objective_composed(pred_c, counts, bp_loss, eval_metric, neg_slp, rep_reg_w, match_loss_w, match_reg_w, reps=(), pred_v=None,
+                          v_mask=None, v_target=None, pred_e=None, e_mask=None, e_target=None):
+    """si_objective in torch ops, written as the reference writes it (train.py:776-813; on CPU tensors the same bits): any dtype, any
+    device.  The caller's tensors are left as they are."""
+    F = torch.nn.functional
+    fn = {"MAE": F.l1_loss, "MSE": F.mse_loss, "SMSE": F.smooth_l1_loss}
+    _objective_crit(bp_loss, "bp_loss"), _objective_crit(eval_metric, "eval_metric")
+    eval_crit = lambda pred, target: fn[eval_metric](F.relu(pred), target)  # noqa: E731
+    bp_crit = lambda pred, target, slp: fn[bp_loss](F.leaky_relu(pred, slp), target)  # noqa: E731
+    pc = pred_c.reshape(-1, 1)
+    c = counts.reshape(-1, 1).to(pc.dtype)
+    dev = pc.device
+    ev = eval_crit(pc.detach(), c)
+    bp = bp_crit(pc, c, neg_slp)
+
+    def side(pred, mask, target):
+        if pred is None or target is None:
+            return torch.tensor([0.0], device=dev), torch.tensor([0.0], device=dev)
+        mask = mask if mask.dtype == torch.bool else mask != 0
+        w = target.detach().to(pred.dtype).masked_fill(~mask, 0)
+        p = _MaskedZeroPassFn.apply(pred, mask)
+        return bp_crit(p, w, neg_slp) * p.size(1), bp_crit(F.relu(p - pc), torch.zeros_like(p), 0) * p.size(1)
+
+    v_loss, v_reg = side(pred_v, v_mask, v_target)
+    e_loss, e_reg = side(pred_e, e_mask, e_target)
+    rep_reg = torch.tensor([0.0], device=dev)
+    for rep in reps:
+        rep_reg = rep_reg + bp_crit(rep, torch.zeros_like(rep), 1) * rep.size(1)
+    bp = bp + rep_reg_w * rep_reg
+    bp = bp + match_loss_w * (v_loss + e_loss)
+    bp = bp + match_reg_w * (v_reg + e_reg)
+    loss = bp.reshape(())
+    terms = torch.stack([t.detach().reshape(()).double() for t in (ev, bp, v_loss, e_loss, v_reg, e_reg, rep_reg)])
+    return loss, terms
+
+
+def _objective_side(pred, mask, target):
+    """(L, pred, mask bytes, target) of one side for the kernels, contiguous; all None and 0 when the side is absent."""
+    if pred is None or target is None:
+        return 0, None, None, None
+    B, L = int(pred.shape[0]), int(pred.numel() // max(int(pred.shape[0]), 1))
+    mask = (mask if mask.dtype == torch.bool else mask != 0).reshape(B, L).contiguous()
+    return L, pred.reshape(B, L).contiguous(), mask, target.detach().reshape(B, L).contiguous()
+
+
+def _objective_rep_arrays(reps, grads=None):
+    n = len(reps)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[r.data_ptr() for r in reps])
+    numel = (ctypes.c_int64 * max(n, 1))(*[int(r.numel()) for r in reps])
+    denom = (ctypes.c_int64 * max(n, 1))(*[int(r.numel()) // int(r.shape[1]) for r in reps])
+    dts = (ctypes.c_int32 * max(n, 1))(*[_objective_dt(r) for r in reps])
+    gp = None if grads is None else (ctypes.c_void_p * max(n, 1))(*[None if g is None else g.data_ptr() for g in grads])
+    return ptrs, numel, denom, dts, gp
+
+
+class _SiObjectiveFn(torch.autograd.Function):
+    """forward: dn_objective_fwd (the pass and its closing launch); backward: ONE launch of dn_objective_bwd, the upstream gradient
+    read on the device.  Nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, pred_c, counts, pred_v, v_mask, v_target, pred_e, e_mask, e_target, cfg, *reps):
+        bp_crit, eval_crit, slope, rrw, mlw, mrw = cfg
+        B = int(pred_c.numel())
+        pc, c = pred_c.reshape(B).contiguous(), counts.detach().reshape(B).contiguous()
+        Lv, pv, mv, wv = _objective_side(pred_v, v_mask, v_target)
+        Le, pe, me, we = _objective_side(pred_e, e_mask, e_target)
+        reps_c = [r.contiguous() for r in reps]
+        dev = require_gpu(pc, c, pv, mv, wv, pe, me, we, *reps_c)
+        ptrs, numel, denom, dts, _ = _objective_rep_arrays(reps_c)
+        terms = torch.empty(7, dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        nb = int(lib().dn_objective_workspace_bytes(B, len(reps_c), numel))
+        if nb == 0:
+            check(-1, "dn_objective_workspace_bytes")
+        ws = torch.empty(nb // 8, dtype=torch.float64, device=dev)
+        dt = lambda t: 0 if t is None else _objective_dt(t)  # noqa: E731
+        launch_tagged("si_objective_fwd", lambda: check(lib().dn_objective_fwd(
+            B, ptr(pc), dt(pc), ptr(c), dt(c), Lv, ptr(pv), dt(pv), ptr(mv), ptr(wv), dt(wv), Le, ptr(pe), dt(pe), ptr(me), ptr(we), dt(we),
+            len(reps_c), ptrs, numel, denom, dts, bp_crit, eval_crit, slope, rrw, mlw, mrw, ptr(terms), ptr(loss), ptr(ws), nb,
+            stream_ptr()), "dn_objective_fwd"))
+        ctx.cfg, ctx.sides = cfg, (Lv, Le)
+        ctx.shapes = (pred_c.shape, None if pred_v is None else pred_v.shape, None if pred_e is None else pred_e.shape)
+        ctx.save_for_backward(pc, c, pv, mv, wv, pe, me, we, *reps_c)
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, gloss, _gterms):
+        pc, c, pv, mv, wv, pe, me, we, *reps = ctx.saved_tensors
+        bp_crit, _, slope, rrw, mlw, mrw = ctx.cfg
+        Lv, Le = ctx.sides
+        need = ctx.needs_input_grad
+        B = int(pc.numel())
+        g = gloss.reshape(()).to(torch.float32).contiguous()
+        dpc = torch.empty_like(pc) if need[0] else None
+        dpv = torch.empty_like(pv) if pv is not None and need[2] else None
+        dpe = torch.empty_like(pe) if pe is not None and need[5] else None
+        dreps = [torch.empty_like(r) if need[9 + i] else None for i, r in enumerate(reps)]
+        ptrs, numel, denom, dts, gp = _objective_rep_arrays(reps, dreps)
+        dt = lambda t: 0 if t is None else _objective_dt(t)  # noqa: E731
+        launch_tagged("si_objective_bwd", lambda: check(lib().dn_objective_bwd(
+            B, ptr(g), ptr(pc), dt(pc), ptr(c), dt(c), Lv, ptr(pv), dt(pv), ptr(mv), ptr(wv), dt(wv), Le, ptr(pe), dt(pe), ptr(me), ptr(we),
+            dt(we), len(reps), ptrs, numel, denom, dts, bp_crit, slope, rrw, mlw, mrw, ptr(dpc), ptr(dpv), ptr(dpe), gp, stream_ptr()),
+            "dn_objective_bwd"))
+        sc, sv, se = ctx.shapes
+        return (None if dpc is None else dpc.view(sc), None, None if dpv is None else dpv.view(sv), None, None,
+                None if dpe is None else dpe.view(se), None, None, None) + tuple(dreps)
+
+
+def si_objective(pred_c, counts, bp_loss, eval_metric, neg_slp, rep_reg_w, match_loss_w, match_reg_w, reps=(), pred_v=None, v_mask=None,
+                 v_target=None, pred_e=None, e_mask=None, e_target=None):
+    """The reference's training objective of one step (train.py:776-813) -> (loss, terms): loss a 0-dim tensor to call backward on,
+    terms [7] float64 on the device, no gradient, in the order SI_OBJECTIVE_TERMS (train.py:815-821).  pred_c, counts [B] or [B, 1];
+    pred_x, x_mask, x_target [B, L_x], a side with no prediction or no target is skipped; reps: up to four representations
+    ([N, H] or [B, L, H]).  bp_loss / eval_metric: "MAE", "MSE" or "SMSE"; the four scalars are Python numbers (schedule_value).
+    Gradients reach pred_c, pred_v, pred_e -- at masked positions too, through the regulariser -- and every representation.
+    The kernels under `with ops.objective_fused()` (ops.SI_OBJECTIVE_FUSED_DEFAULT) for fp32 / bf16 CUDA tensors, else
+    si_objective_composed."""
+    reps = tuple(reps)
+    bp_c, ev_c = _objective_crit(bp_loss, "bp_loss"), _objective_crit(eval_metric, "eval_metric")
+    if pred_v is None or v_target is None:
+        pred_v = v_mask = v_target = None
+    if pred_e is None or e_target is None:
+        pred_e = e_mask = e_target = None
+    if not (objective_fused_enabled() and si_objective_supported(pred_c, counts, reps, pred_v, v_target, pred_e, e_target)):
+        return launch_tagged("si_objective_composed", lambda: si_objective_composed(
+            pred_c, counts, bp_loss, eval_metric, neg_slp, rep_reg_w, match_loss_w, match_reg_w, reps, pred_v, v_mask, v_target, pred_e,
+            e_mask, e_target))
+    slope = float(_np.float32(neg_slp))                                        # (torch's leaky_relu multiplies by the slope as a float)
+    cfg = (bp_c, ev_c, slope, float(rep_reg_w), float(match_loss_w), float(match_reg_w))
+    return _SiObjectiveFn.apply(pred_c, counts, pred_v, v_mask, v_target, pred_e, e_mask, e_target, cfg, *reps)
+
+
+def si_eval_errors_composed(pred_c, counts, pred_v=None, v_target=None, pred_e=None, e_target=None):
+    """(AE, SE, NED, EED, cls) per pair in torch ops, as evaluate_epoch computes them (train.py:1111, :1126, :1164-1165); cls =
+    (counts > 0) + 2 (relu(pred_c) > 0) as int32."""
+    F = torch.nn.functional
+    pc = F.relu(pred_c.detach().reshape(-1).float())
+    c = counts.reshape(-1).float()
+    ae = F.l1_loss(pc, c, reduction="none")
+    se = F.mse_loss(pc, c, reduction="none")
+
+    def dist(pred, target):
+        if pred is None or target is None:
+            return torch.zeros_like(ae)
+        return F.l1_loss(F.relu(pred.detach().float()), target.float(), reduction="none").reshape(ae.numel(), -1).sum(dim=1)
+
+    cls = (c > 0).to(I32) + 2 * (pc > 0).to(I32)
+    return ae, se, dist(pred_v, v_target), dist(pred_e, e_target), cls
+
+
+def si_eval_errors(pred_c, counts, pred_v, v_target, pred_e, e_target, offset, ae, se, ned, eed, cls):
+    """The per-pair errors of one evaluation batch written at [offset, offset + B) of the epoch's buffers (float32 ae, se, ned, eed and
+    int32 cls of one length): ONE launch of dn_objective_eval under `with ops.objective_fused()` for fp32 / bf16 CUDA tensors, else
+    si_eval_errors_composed and five slice copies.  NED / EED run over all positions, no mask.  Nothing is read back."""
+    if pred_v is None or v_target is None:
+        pred_v = v_target = None
+    if pred_e is None or e_target is None:
+        pred_e = e_target = None
+    B, cap = int(pred_c.numel()), int(ae.numel())
+    if offset < 0 or offset + B > cap:
+        raise ValueError("si_eval_errors: %d pairs at offset %d do not fit the %d entries of the epoch's buffers" % (B, offset, cap))
+    if not (objective_fused_enabled() and si_objective_supported(pred_c, counts, (), pred_v, v_target, pred_e, e_target) and ae.is_cuda):
+        outs = launch_tagged("si_eval_composed", lambda: si_eval_errors_composed(pred_c, counts, pred_v, v_target, pred_e, e_target))
+        for buf, o in zip((ae, se, ned, eed, cls), outs):
+            buf[offset:offset + B] = o
+        return
+    pc, c = pred_c.detach().reshape(B).contiguous(), counts.reshape(B).contiguous()
+    side = lambda p, w: (0, None, None) if p is None else (int(p.numel()) // B, p.detach().reshape(B, -1).contiguous(),  # noqa: E731
+                                                           w.reshape(B, -1).contiguous())
+    (Lv, pv, wv), (Le, pe, we) = side(pred_v, v_target), side(pred_e, e_target)
+    require_gpu(pc, c, pv, wv, pe, we, ae, se, ned, eed, cls)
+    dt = lambda t: 0 if t is None else _objective_dt(t)  # noqa: E731
+    launch_tagged("si_objective_eval", lambda: check(lib().dn_objective_eval(
+        B, ptr(pc), dt(pc), ptr(c), dt(c), Lv, ptr(pv), dt(pv), ptr(wv), dt(wv), Le, ptr(pe), dt(pe), ptr(we), dt(we), int(offset), cap,
+        ptr(ae), ptr(se), ptr(ned), ptr(eed), ptr(cls), stream_ptr()), "dn_objective_eval"))

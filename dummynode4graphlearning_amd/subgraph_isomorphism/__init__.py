@@ -17,3 +17,4 @@ from .edge_seq import EdgeSeqModel  # noqa: F401
 from .cnn import CNN, CNNLayer  # noqa: F401
 from .rnn import RNN, RNNLayer  # noqa: F401
 from .txl import TXLFF, MixtureDict, TransformerXL, TXLAttn, TXLLayer  # noqa: F401
+from .objective import SIEvalMeter, SIObjective, SITrainMeter, anneal_fn, cyclical_fn, schedule_value  # noqa: F401

@@ -1395,6 +1395,51 @@ int dn_svm_smo_f64(int64_t num_matrices, int64_t n, const double* K, int64_t num
                    const int32_t* list, int64_t num_rows, const int32_t* rows, int32_t max_len, double eps, int32_t iters_per_launch,
                    double* alpha, double* grad, double* rho, int64_t* iterations, int32_t* status, dn_stream_t stream);
 
+/* ---- the SI training objective and the epoch's per-sample errors (dn_objective.hip) ----
+ * The objective of subgraph_isomorphism/train.py:776-821 and the per-sample errors of evaluate_epoch (train.py:1101-1173).  With
+ * crit(d) = |d| (MAE), d^2 (MSE) or smooth-L1 at beta 1 (SMSE), s = neg_slp, m the mask and B the pairs:
+ *   eval = 1/B sum_b crit_eval(relu(pred_c_b) - c_b)          bp = 1/B sum_b crit(lrelu(pred_c_b, s) - c_b)
+ *   x_loss = 1/B sum_bj crit(lrelu(m p_bj, s) - m w_bj)       x_reg = 1/B sum_bj crit(relu(m p_bj - pred_c_b))     (x = v, e)
+ *   rep_reg = sum_r (sum crit(rep_r)) / rep_denom[r]          (rep_denom = numel / size(1))
+ *   loss = bp + rep_reg_w rep_reg + match_loss_w (v_loss + e_loss) + match_reg_w (v_reg + e_reg)
+ * x_reg runs over ALL positions (a masked one enters as 0) and its gradient reaches pred_x there too.
+ *   pred_c, counts [B]; pred_x, x_mask (bytes, non-zero = kept), x_target [B, L_x], a side is absent when all three are NULL and
+ *   L_x == 0; reps / rep_numel / rep_denom / rep_dt: HOST arrays of num_reps <= DN_OBJECTIVE_MAX_REPS entries.  Every tensor is
+ *   contiguous and fp32 or bf16, by its own *_dt code; gradients come back in the dtype of their input.
+ *   dn_objective_fwd   terms [7] doubles = {eval, loss, v_loss, e_loss, v_reg, e_reg, rep_reg} (the order train.py:815-821 reads
+ *                      them), loss a float; workspace of dn_objective_workspace_bytes bytes (the workgroups' partial sums, added
+ *                      in index order by a closing launch).  fp64 accumulation, no atomics, the grid depends on the shapes only:
+ *                      two runs give the same bits.
+ *   dn_objective_bwd   ONE launch: grad_loss (device, a float) times the gradient of loss at pred_c, pred_v, pred_e and every
+ *                      representation; an output that is NULL is not computed.
+ *   dn_objective_eval  per pair, at [offset, offset + B) of buffers of `capacity` entries: ae = |relu(pred_c) - c|, se = ae^2,
+ *                      ned / eed = sum_j |relu(p_bj) - w_bj| over all positions (no mask; 0 for an absent side),
+ *                      cls = (c > 0) + 2 (relu(pred_c) > 0).
+ * Arguments are checked on the host before any launch (-1 and a message); nothing reads device memory back. */
+#define DN_OBJECTIVE_MAE 0
+#define DN_OBJECTIVE_MSE 1
+#define DN_OBJECTIVE_SMSE 2
+#define DN_OBJECTIVE_F32 0
+#define DN_OBJECTIVE_BF16 1
+#define DN_OBJECTIVE_MAX_REPS 4
+size_t dn_objective_workspace_bytes(int64_t B, int32_t num_reps, const int64_t* rep_numel);
+int dn_objective_fwd(int64_t B, const void* pred_c, int32_t pred_c_dt, const void* counts, int32_t counts_dt, int64_t Lv, const void* pred_v,
+                     int32_t pred_v_dt, const uint8_t* v_mask, const void* v_target, int32_t v_target_dt, int64_t Le, const void* pred_e,
+                     int32_t pred_e_dt, const uint8_t* e_mask, const void* e_target, int32_t e_target_dt, int32_t num_reps,
+                     const void* const* reps, const int64_t* rep_numel, const int64_t* rep_denom, const int32_t* rep_dt, int32_t bp_crit,
+                     int32_t eval_crit, double neg_slp, double rep_reg_w, double match_loss_w, double match_reg_w, double* terms,
+                     float* loss, void* workspace, size_t workspace_bytes, dn_stream_t stream);
+int dn_objective_bwd(int64_t B, const float* grad_loss, const void* pred_c, int32_t pred_c_dt, const void* counts, int32_t counts_dt,
+                     int64_t Lv, const void* pred_v, int32_t pred_v_dt, const uint8_t* v_mask, const void* v_target, int32_t v_target_dt,
+                     int64_t Le, const void* pred_e, int32_t pred_e_dt, const uint8_t* e_mask, const void* e_target, int32_t e_target_dt,
+                     int32_t num_reps, const void* const* reps, const int64_t* rep_numel, const int64_t* rep_denom, const int32_t* rep_dt,
+                     int32_t bp_crit, double neg_slp, double rep_reg_w, double match_loss_w, double match_reg_w, void* d_pred_c,
+                     void* d_pred_v, void* d_pred_e, void* const* d_reps, dn_stream_t stream);
+int dn_objective_eval(int64_t B, const void* pred_c, int32_t pred_c_dt, const void* counts, int32_t counts_dt, int64_t Lv, const void* pred_v,
+                      int32_t pred_v_dt, const void* v_target, int32_t v_target_dt, int64_t Le, const void* pred_e, int32_t pred_e_dt,
+                      const void* e_target, int32_t e_target_dt, int64_t offset, int64_t capacity, float* ae, float* se, float* ned,
+                      float* eed, int32_t* cls, dn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
